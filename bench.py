@@ -1,6 +1,16 @@
 """Benchmark: the acoustic volume render path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mode MODE] [--workload NAME]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times K steps and prints one JSON
+line (`value`, `ms_per_step`).  `--dump-outputs DIR` also writes what the last
+timed step returned as DIR/<name>.npy; the inputs are seeded, so two builds
+run with the same arguments can be compared array for array.  `--full` adds
+every other measurement to the line: the serial IR latency (eager and
+HIP-graph replay), the graph-replay throughput, the per-kernel roofline phase,
+the CPU baseline and, in pose mode, the inference through the reference
+network (`--no-cpu-baseline` / `--no-network` leave those two out of it).
 
 Modes (a "step" is one pass of the hot path over one unit of synthetic input):
 
@@ -134,14 +144,19 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--mode", default="pose", choices=sorted(MODES))
     ap.add_argument("--workload", default=None, help="default: the mode's workload")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: IR latency, graph-replay throughput, roofline phase, "
+                         "CPU baseline and (pose mode) inference through the reference network")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--network", action="store_true",
                     help="ray-shard mode: render through the reference network (AVRModel, avr_simu.yml "
                          "model block, random init, --mlp-dtype MLPs, fused rounding-exact head) instead of "
                          "the stub's resident outputs")
     ap.add_argument("--no-network", action="store_true",
-                    help="pose mode: skip the config-2 inference through the reference network")
+                    help="pose mode: --full without the config-2 inference through the reference network")
     ap.add_argument("--poses", type=int, default=16,
                     help="distinct synthetic poses cycled over the steps")
     ap.add_argument("--graph-ring", type=int, default=12,
@@ -235,6 +250,27 @@ def timed(run, world, dev):
 def whole_job_rate(units_per_rank, world, steps, elapsed_max):
     """value: units every rank processed over the slowest rank's time."""
     return units_per_rank * world * steps / elapsed_max
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, outputs, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: write {name: tensor} as DIR/<name>.npy, float32 (float64
+    tensors stay float64).  The arrays share `limit` bytes equally; a larger
+    one is written as a fixed sample of its elements (seeded choice, sorted,
+    so two builds sample the same positions)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    share = limit // max(1, len(outputs))
+    for name, t in outputs.items():
+        t = t.detach().cpu()
+        a = (t if t.dtype == torch.float64 else t.float()).numpy()
+        if a.nbytes > share:
+            keep = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(keep)]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 # ----------------------------------------------------------------------------
@@ -577,7 +613,7 @@ def bench_pose(args, w, world, rank, dev):
     while len(renderers) < n_streams:
         add_renderer()
     del renderers[n_streams:]
-    timer = KernelTimer(args.steps)
+    timer = KernelTimer(args.steps if args.full else 0)
     renderers[0].kernel_timer = timer
     pose = [0]
     streams = [torch.cuda.current_stream(dev)] + [torch.cuda.Stream(dev) for _ in range(n_streams - 1)]
@@ -589,14 +625,63 @@ def bench_pose(args, w, world, rank, dev):
             return renderers[k].render_ir(rays_o[i], tx[i], dtx[i])
 
     def run(n, ns):
+        last = None
         for i in range(n):
             with torch.cuda.stream(streams[i % ns]):
-                step(i % ns)
+                last = step(i % ns)
+        return last
 
     torch.manual_seed(rank)
     run(args.warmup, n_streams)
     torch.cuda.synchronize()
 
+    extra = _pose_extras_before(args, renderers, streams, timer, pose, step, run,
+                                (rays_o, tx, dtx)) if args.full else None
+
+    # throughput (the reported value): K independent single-pose renders on
+    # the streams round-robin, issued eagerly.  The timed steps start from
+    # pose 0 and a fixed jitter stream whatever ran before them, so a plain
+    # and a --full run time, and --dump-outputs writes, the same renders
+    pose[0] = 0
+    torch.manual_seed(rank)
+    last = []
+    elapsed, t_issue = timed(lambda: last.append(run(args.steps, n_streams)), world, dev)
+    spectrum, ir = last[0]
+    outputs = {"spectrum": spectrum, "ir": ir}
+    value = whole_job_rate(w.ray_samples, world, args.steps, elapsed)
+    res = _base_result(args, w, world, value, elapsed, "f32" if dt == torch.float32 else "f16-storage/f32-math")
+    res.update({
+        "host_issue_ms_per_step": t_issue * 1e3 / args.steps,
+        "throughput_path": "eager issue, 2 HIP streams round-robin (one ctypes render-core call per pose)",
+        "streams": n_streams,
+        "config": {"workload": w.name, "mode": "pose", "rays": R, "samples": S, "T": T, "freq_bins": w.F,
+                   "poses_per_step": B, "distinct_poses": P,
+                   "parallelism": f"poses x{world} (no data-path collective)",
+                   "pipelining": f"{n_streams} HIP streams, consecutive poses round-robin, "
+                                 "one signal buffer and one graph ring per stream"},
+    })
+    if args.full:
+        latency_ms, latency_eager_ms, run_graph = extra
+        elapsed_graph, t_issue_graph = timed(lambda: run_graph(args.steps, n_streams), world, dev)
+        res.update({
+            "ir_render_ms_per_pose": latency_ms / B,
+            "ir_render_path": "HIP-graph replay (avr_amd.graph.GraphedRender), host poses, synchronized per pose",
+            "ir_render_ms_per_pose_eager": latency_eager_ms / B,
+            "ms_per_step_graph": elapsed_graph * 1e3 / args.steps,
+            "host_issue_ms_per_step_graph": t_issue_graph * 1e3 / args.steps,
+            "roofline": roofline(w, timer, dt),
+        })
+    return res, outputs
+
+
+def _pose_extras_before(args, renderers, streams, timer, pose, step, run, poses):
+    """--full, pose mode: the measurements taken between the warm-up and the
+    timed steps.  Returns (graph latency ms, eager latency ms, run_graph);
+    `timer` holds the roofline phase's events."""
+    from avr_amd.graph import GraphedRender
+
+    rays_o, tx, dtx = poses
+    P, n_streams = args.poses, len(renderers)
     # latency: one pose at a time on one stream (IR render ms/pose), issued
     # eagerly and replayed from a HIP graph (avr_amd.graph.GraphedRender:
     # same kernels and results bit for bit, no per-launch host work)
@@ -611,8 +696,6 @@ def bench_pose(args, w, world, rank, dev):
         return (time.perf_counter() - t0) * 1e3 / n_lat
 
     latency_eager_ms = latency(lambda: step(0))
-    from avr_amd.graph import GraphedRender
-
     graphed = GraphedRender(renderers[0], ring=args.graph_ring)
     # poses handed over from the host, as a data loader yields them
     # (avr_runner.py:168): staged in the replay's pinned buffer, no copy
@@ -638,16 +721,15 @@ def bench_pose(args, w, world, rank, dev):
     torch.cuda.synchronize()
     timer.enabled = False
 
-    # throughput: K independent single-pose renders on 2 streams, issued
-    # eagerly (the reported value) and, as a second measurement, replayed
-    # from each stream's HIP graph ring (the same kernels and results,
-    # tests/test_gpu_graph.py; host poses staged in pinned memory).  Since
-    # round 3 the eager issue (~75 us of host work per pose) no longer gates
-    # a ~120 us pose, and it keeps each stream's kernels back to back, while
-    # consecutive graph replays on one stream leave 15-23 us between them
-    # (kernel trace): eager measured 0.1186-0.1226 against
-    # 0.1210-0.1308 ms per pose for the replays over 4 runs of the driver's
-    # command (tools/gpu_eager_graph.sh)
+    # second throughput measurement, timed after the eager one: the same K
+    # renders replayed from each stream's HIP graph ring (the same kernels
+    # and results, tests/test_gpu_graph.py; host poses staged in pinned
+    # memory).  Since round 3 the eager issue (~75 us of host work per pose)
+    # no longer gates a ~120 us pose, and it keeps each stream's kernels back
+    # to back, while consecutive graph replays on one stream leave 15-23 us
+    # between them (kernel trace): eager measured 0.1186-0.1226
+    # against 0.1210-0.1308 ms per pose for the replays over 4 runs of the
+    # driver's command (tools/gpu_eager_graph.sh)
     graphs = [graphed] + [GraphedRender(rr, ring=args.graph_ring) for rr in renderers[1:]]
 
     def run_graph(n, ns):
@@ -661,27 +743,7 @@ def bench_pose(args, w, world, rank, dev):
 
     run_graph(max(args.warmup, (graphed.ring + 2) * n_streams), n_streams)  # captures + warm replays
     torch.cuda.synchronize()
-    elapsed, t_issue = timed(lambda: run(args.steps, n_streams), world, dev)
-    elapsed_graph, t_issue_graph = timed(lambda: run_graph(args.steps, n_streams), world, dev)
-    value = whole_job_rate(w.ray_samples, world, args.steps, elapsed)
-    res = _base_result(args, w, world, value, elapsed, "f32" if dt == torch.float32 else "f16-storage/f32-math")
-    res.update({
-        "ir_render_ms_per_pose": latency_ms / B,
-        "ir_render_path": "HIP-graph replay (avr_amd.graph.GraphedRender), host poses, synchronized per pose",
-        "ir_render_ms_per_pose_eager": latency_eager_ms / B,
-        "host_issue_ms_per_step": t_issue * 1e3 / args.steps,
-        "throughput_path": "eager issue, 2 HIP streams round-robin (one ctypes render-core call per pose)",
-        "ms_per_step_graph": elapsed_graph * 1e3 / args.steps,
-        "host_issue_ms_per_step_graph": t_issue_graph * 1e3 / args.steps,
-        "streams": n_streams,
-        "config": {"workload": w.name, "mode": "pose", "rays": R, "samples": S, "T": T, "freq_bins": w.F,
-                   "poses_per_step": B, "distinct_poses": P,
-                   "parallelism": f"poses x{world} (no data-path collective)",
-                   "pipelining": f"{n_streams} HIP streams, consecutive poses round-robin, "
-                                 "one signal buffer and one graph ring per stream"},
-        "roofline": roofline(w, timer, dt),
-    })
-    return res
+    return latency_ms, latency_eager_ms, run_graph
 
 
 def bench_ray_shard(args, w, world, rank, dev):
@@ -713,7 +775,7 @@ def bench_ray_shard(args, w, world, rank, dev):
     P = args.poses
     rays_o, tx, dtx = _poses(w, P, dev, pg)
     renderer = AVRRender(net, **w.render).to(dev)
-    timer = KernelTimer(args.steps)
+    timer = KernelTimer(args.steps if args.full else 0)
     renderer.kernel_timer = timer
     sharded = RayShardedRender(renderer, shard=(0, shard_of) if shard_of else None)
     pose = [0]
@@ -726,17 +788,25 @@ def bench_ray_shard(args, w, world, rank, dev):
             return out, spectrum_to_ir(out)
 
     def run(n):
+        last = None
         for _ in range(n):
-            step()
+            last = step()
+        return last
 
     torch.manual_seed(7)  # same CPU jitter stream on every rank
     run(args.warmup)
     torch.cuda.synchronize()
-    timer.enabled = True
-    run(args.steps)
-    torch.cuda.synchronize()
-    timer.enabled = False
-    elapsed, t_issue = timed(lambda: run(args.steps), world, dev)
+    if args.full:  # roofline phase: HIP events around the dominant kernel's launches
+        timer.enabled = True
+        run(args.steps)
+        torch.cuda.synchronize()
+        timer.enabled = False
+    # the timed steps start from pose 0 and a fixed jitter stream whatever ran before them
+    pose[0] = 0
+    torch.manual_seed(7)
+    last = []
+    elapsed, t_issue = timed(lambda: last.append(run(args.steps)), world, dev)
+    outputs = dict(zip(("spectrum", "ir"), last[0]))
     if shard_of:  # this shard's ray-samples per second (one rank's rate)
         value = whole_job_rate(B * Rl * S, 1, args.steps, elapsed)
     else:
@@ -744,7 +814,6 @@ def bench_ray_shard(args, w, world, rank, dev):
     res = _base_result(args, w, world, value, elapsed, "f32" if dt == torch.float32 else "f16-storage/f32-math")
     # with the network the fused head replaces the ray reduction: the head's
     # own events (FusedHeadCore, rounding-exact 16-bit head)
-    rf = roofline(w, timer, dt) if not args.network else head_roofline(w, timer)
     if args.network:
         res["dtype"] = args.mlp_dtype + " MLP / f32 render"
         res["data"] = "synthetic poses; AVRModel (avr_simu.yml model block), random init, evaluated per ray shard"
@@ -759,9 +828,10 @@ def bench_ray_shard(args, w, world, rank, dev):
                                    if shard_of else
                                    f"rays x{world}, one RCCL all-reduce of the [B,F,2] spectrum per pose"),
                    "network": "AVRModel (avr_simu.yml)" if args.network else "stub (outputs resident in HBM)"},
-        "roofline": rf,
     })
-    return res
+    if args.full:
+        res["roofline"] = roofline(w, timer, dt) if not args.network else head_roofline(w, timer)
+    return res, outputs
 
 
 def bench_ddp_train(args, w, world, rank, dev):
@@ -793,24 +863,34 @@ def bench_ddp_train(args, w, world, rank, dev):
     def step():
         i = it[0] % P
         it[0] += 1
-        ts(targets[i], rays_o[i], tx[i], dtx[i])
+        return ts(targets[i], rays_o[i], tx[i], dtx[i])
 
     def run(n):
+        last = None
         for _ in range(n):
-            step()
+            last = step()
+        return last
 
     torch.manual_seed(rank)
     run(args.warmup)
     torch.cuda.synchronize()
-    # roofline phase: HIP events around the optimizer's Adam launches (the
-    # step's largest single kernel, HBM-bound), then the timed region
-    pool = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
     used = []
-    ts.adam_events = lambda: used.append(pool[len(used)]) or used[-1] if len(used) < len(pool) else None
-    run(args.steps)
-    torch.cuda.synchronize()
-    ts.adam_events = None
-    elapsed, t_issue = timed(lambda: run(args.steps), world, dev)
+    if args.full:
+        # roofline phase: HIP events around the optimizer's Adam launches (the
+        # step's largest single kernel, HBM-bound), then the timed region
+        pool = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                for _ in range(args.steps)]
+        ts.adam_events = lambda: used.append(pool[len(used)]) or used[-1] if len(used) < len(pool) else None
+        run(args.steps)
+        torch.cuda.synchronize()
+        ts.adam_events = None
+    last = []
+    elapsed, t_issue = timed(lambda: last.append(run(args.steps)), world, dev)
+    # the training step returns (total loss, its 8 terms), or None for a skipped (NaN) step
+    outputs = {}
+    if last[0] is not None:
+        outputs = {"total_loss": last[0][0].reshape(1),
+                   "losses": torch.stack([x.reshape(()).float().cpu() for x in last[0][1]])}
     value = whole_job_rate(w.ray_samples, world, args.steps, elapsed)
     n_params = sum(p.numel() for p in r.parameters())
     n_trained = sum(p.numel() for p in r.parameters() if p.requires_grad)
@@ -823,9 +903,10 @@ def bench_ddp_train(args, w, world, rank, dev):
                    "model": "AVRModel_complex (6 hash grids, RAF MLP widths)",
                    "params": n_params, "grad_allreduce_bytes": 4 * n_params if world > 1 else 0,
                    "parallelism": f"dp{world} (DDP, RCCL bucketed gradient all-reduce)"},
-        "roofline": adam_roofline(used, n_trained),
     })
-    return res
+    if args.full:
+        res["roofline"] = adam_roofline(used, n_trained)
+    return res, outputs
 
 
 def main(argv=None):
@@ -854,11 +935,14 @@ def main(argv=None):
 
     w = WORKLOADS[args.workload]
     fn = {"pose": bench_pose, "ray-shard": bench_ray_shard, "ddp-train": bench_ddp_train}[args.mode]
-    result = fn(args, w, world, rank, dev)
+    result, outputs = fn(args, w, world, rank, dev)
     if args.oversubscribe:
         result["oversubscribed"] = f"{world} ranks on cuda:0 over gloo (launcher rehearsal, not a scaling number)"
-    attach_cpu_baseline(result, args, w, world, rank)
-    if rank == 0 and world == 1 and args.mode == "pose" and w.name.startswith("c2_meshrir") \
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
+    if args.full:
+        attach_cpu_baseline(result, args, w, world, rank)
+    if args.full and rank == 0 and world == 1 and args.mode == "pose" and w.name.startswith("c2_meshrir") \
             and not args.no_network:
         result["network_inference"] = network_inference(w, dev)
     if rank == 0:

@@ -158,6 +158,39 @@ def test_cpu_baseline_in_the_two_rank_line_gloo():
         assert "cpu_baseline" not in out[1][mode]
 
 
+def test_plain_run_by_default():
+    """--full and --dump-outputs are off unless given."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_npy(tmp_path):
+    """One .npy per output, float32 (float64 kept), values unchanged; an array
+    over its share of the byte limit is written as the same sorted sample of
+    its elements every time."""
+    import numpy as np
+
+    big = torch.arange(1000, dtype=torch.float32)
+    outs = {"spectrum": torch.arange(12, dtype=torch.float32).reshape(1, 6, 2) / 7,
+            "half": torch.tensor([0.5, -2.0], dtype=torch.float16),
+            "wide": torch.tensor([1 / 3], dtype=torch.float64),
+            "big": big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outs, limit=4 * 400)  # 400 bytes each
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in outs}
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == sorted(n + ".npy" for n in outs)
+    assert got["spectrum"].dtype == np.float32 and got["spectrum"].shape == (1, 6, 2)
+    assert np.array_equal(got["spectrum"], outs["spectrum"].numpy())
+    assert got["half"].dtype == np.float32 and got["half"].tolist() == [0.5, -2.0]
+    assert got["wide"].dtype == np.float64 and got["wide"][0] == 1 / 3
+    assert got["big"].shape == (100,) and np.all(np.diff(got["big"]) > 0)  # distinct elements, in order
+    assert np.array_equal(got["big"], np.load(tmp_path / "b" / "big.npy"))
+    assert sum(a.nbytes for a in got.values()) <= 4 * 400
+    assert bench.DUMP_LIMIT_BYTES == 64 * 2 ** 20
+
+
 def test_cpu_leg_threads(monkeypatch):
     monkeypatch.setenv("AVR_CPU_THREADS", "3")
     assert bench.cpu_leg_threads() == 3

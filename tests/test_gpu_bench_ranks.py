@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _bench(*args, timeout=400):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--oversubscribe",
-           "--steps", "3", "--warmup", "1", "--cpu-budget", "0.2", *args]
+           "--steps", "3", "--warmup", "1", "--full", "--cpu-budget", "0.2", *args]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, (p.returncode, p.stdout[-3000:], p.stderr[-3000:])

@@ -23,7 +23,7 @@ if [ "${SKIP_SMOKE:-0}" != 1 ]; then
   tail -1 $OUT/smoke.log
 fi
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
-  step bench 400 python bench.py --gpus 1 --steps 20 --warmup 5
+  step bench 400 python bench.py --full --gpus 1 --steps 20 --warmup 5
   tail -1 $OUT/bench.log > $OUT/bench.json
   python -c "import json; d=json.load(open('$OUT/bench.json')); print('bench', d['value'], d['ms_per_step'], d['ir_render_ms_per_pose'], d['roofline']['avg_launch_ms'], d['network_inference']['ms_per_pose'])"
 fi
