@@ -13,6 +13,12 @@ from .renderer import (  # noqa: F401
     spectrum_to_ir,
 )
 from .criterion import Criterion  # noqa: F401
+from .metrics import (  # noqa: F401
+    MetricAccumulator,
+    calculate_metrics,
+    metric_cal,
+    metric_rows,
+)
 from .options import KernelOptions  # noqa: F401
 from . import workloads  # noqa: F401
 

@@ -35,6 +35,13 @@ int device_cus();
 int launch_irfft(int B, int F, const float* spec, const float* spec2, const float* tw, float* ir,
                  float* ir2, void* stream);
 
+// MR-STFT of the criterion's resolutions 0-2 on two batches of IRs [B][n]
+// (criterion.hip), the validation metrics' multi_stft: *out (device) = the
+// mean of the three resolutions' terms; ws holds mr3_workspace() bytes.
+int mr3_workspace(int B, int n, int64_t* bytes);
+int launch_mr3(int B, int n, const float* pred_time, const float* ori_time, const float* wtab,
+               const float* tw512, void* ws, int64_t ws_bytes, float* out, void* stream);
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ---------------------------------------------------------------- MFMA operand hold

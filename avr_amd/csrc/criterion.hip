@@ -273,6 +273,35 @@ __global__ __launch_bounds__(kThreads) void crit_stft_kernel(CritPlan P,
     }
 }
 
+// MR-STFT reduction, shared by the criterion and the validation metrics
+// (avr_metrics): per (item, resolution) sums over that pair's tiles ...
+__device__ __forceinline__ void mr_item_stats(const CritPlan& P, const CritWs& W, int b, int q) {
+    const int mr_tiles = P.r[kEnergy].tile_f;
+    const int t0 = P.r[q].tile_f, t1 = P.r[q + 1].tile_f;
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int t = t0; t < t1; ++t)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) a[c] += W.part[((int64_t)b * mr_tiles + t) * 4 + c];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) W.stat[(b * 4 + q) * 4 + c] = a[c];
+}
+// ... then resolution q's spectral-convergence, log-magnitude and
+// linear-magnitude terms over the batch, items in order
+__device__ __forceinline__ void mr_res_terms(const CritPlan& P, const CritWs& W, int q, float* out) {
+    const int B = P.B;
+    float sc = 0.f, lg = 0.f, ln = 0.f;
+    for (int b = 0; b < B; ++b) {
+        const float* st = W.stat + (b * 4 + q) * 4;
+        sc += sqrtf(st[0]) / sqrtf(st[1]);
+        lg += st[2];
+        ln += st[3];
+    }
+    const float cnt = (float)B * (float)P.r[q].K * (float)P.r[q].M;
+    out[0] = sc / (float)B;
+    out[1] = lg / cnt;
+    out[2] = ln / cnt;
+}
+
 // One workgroup of 1024 lanes: every remaining sum, the losses, and the
 // statistics the backward needs.  losses[6] = spec, amp, angle, time,
 // energy, mrstft (weighted as criterion.py does).
@@ -316,33 +345,10 @@ __global__ __launch_bounds__(kRedThreads) void crit_reduce_kernel(CritPlan P,
     for (int c = 0; c < 6; ++c) tot[c] = red[c][0];
     __syncthreads();
     // ---- MR-STFT: per (item, resolution) sums over that pair's tiles
-    const int mr_tiles = P.r[kEnergy].tile_f;
-    if (tid < 4 * B) {
-        const int b = tid >> 2, q = tid & 3;
-        const int t0 = P.r[q].tile_f, t1 = P.r[q + 1].tile_f;
-        float a[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int t = t0; t < t1; ++t)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) a[c] += W.part[((int64_t)b * mr_tiles + t) * 4 + c];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) W.stat[(b * 4 + q) * 4 + c] = a[c];
-    }
+    if (tid < 4 * B) mr_item_stats(P, W, tid >> 2, tid & 3);
     __threadfence_block();
     __syncthreads();
-    if (tid < 4) {
-        const int q = tid;
-        float sc = 0.f, lg = 0.f, ln = 0.f;
-        for (int b = 0; b < B; ++b) {
-            const float* st = W.stat + (b * 4 + q) * 4;
-            sc += sqrtf(st[0]) / sqrtf(st[1]);
-            lg += st[2];
-            ln += st[3];
-        }
-        const float cnt = (float)B * (float)P.r[q].K * (float)P.r[q].M;
-        qsum[q][0] = sc / (float)B;
-        qsum[q][1] = lg / cnt;
-        qsum[q][2] = ln / cnt;
-    }
+    if (tid < 4) mr_res_terms(P, W, tid, qsum[tid]);
     // ---- energy decay curves (criterion.py:80-83), one lane per item
     const int M = P.M4;
     if (tid < B) {
@@ -580,7 +586,53 @@ __global__ __launch_bounds__(kThreads) void crit_bwd_spec_kernel(CritPlan P,
     grad[i] = make_float2(dre, dim);
 }
 
+// utils/metric.py:31-32: the MR-STFT of resolutions 0-2 alone (fft 512/256/
+// 128), from the same tiles' partial sums, mean of the three.
+constexpr int kMetricRes = 3;
+__global__ __launch_bounds__(kRedThreads) void crit_mr3_reduce_kernel(CritPlan P, CritWs W,
+                                                                      float* __restrict__ out) {
+    __shared__ float qsum[kMetricRes][3];
+    const int tid = threadIdx.x;
+    if (tid < 4 * P.B && (tid & 3) < kMetricRes) mr_item_stats(P, W, tid >> 2, tid & 3);
+    __threadfence_block();
+    __syncthreads();
+    if (tid < kMetricRes) mr_res_terms(P, W, tid, qsum[tid]);
+    __syncthreads();
+    if (tid == 0) {
+        float mr = 0.f;
+        for (int q = 0; q < kMetricRes; ++q) mr += (qsum[q][0] + qsum[q][1]) + qsum[q][2];
+        *out = mr / (float)kMetricRes;
+    }
+}
+
 }  // namespace
+
+namespace avr {
+
+int mr3_workspace(int B, int n, int64_t* bytes) {
+    CritPlan P;
+    if (int e = make_plan(B, n / 2 + 1, nullptr, &P)) return e;
+    *bytes = carve(P, nullptr).bytes;
+    return 0;
+}
+
+int launch_mr3(int B, int n, const float* pred_time, const float* ori_time, const float* wtab,
+               const float* tw512, void* ws, int64_t ws_bytes, float* out, void* stream) {
+    CritPlan P;
+    if (int e = make_plan(B, n / 2 + 1, nullptr, &P)) return e;
+    CritWs W = carve(P, ws);
+    AVR_REQUIRE(ws_bytes >= W.bytes, "avr_metrics: MR-STFT workspace too small");
+    AVR_REQUIRE(B <= 256, "avr_metrics: at most 256 items per call");
+    // the tiles of resolutions 0..2 come first in the criterion's tile order
+    hipLaunchKernelGGL(crit_stft_kernel, dim3(P.r[kMetricRes].tile_f, B), dim3(kThreads), 0,
+                       as_stream(stream), P, pred_time, ori_time, wtab,
+                       reinterpret_cast<const float2*>(tw512), W);
+    if (int e = check_launch("crit_stft_kernel")) return e;
+    hipLaunchKernelGGL(crit_mr3_reduce_kernel, dim3(1), dim3(kRedThreads), 0, as_stream(stream), P, W, out);
+    return check_launch("crit_mr3_reduce_kernel");
+}
+
+}  // namespace avr
 
 extern "C" int avr_criterion_window_len(void) { return window_len(); }
 

@@ -563,6 +563,30 @@ int avr_das_bwd(int32_t n, const float* steer, const float* angles, const float*
                 float w_reg, float w_ce, const float* grad_losses, void* workspace,
                 int64_t workspace_bytes, float* grad_pred_time, void* stream);
 
+/* ---- validation metrics (utils/metric.py:8-136, avr_runner.py:374-407) --
+ * ori, pred: impulse responses [B][n] fp32; n even, 256 < n <= 12288 (the
+ * criterion's limits), B <= 256, 1 <= window <= n (the amplitude metric's
+ * box, 32 in the reference), fs > 0, s50 = int(0.05 * fs) computed by the
+ * host in double.  ir_twiddle = avr_ir_twiddle(n); win_table and tw512 are
+ * the criterion's tables (avr_criterion_fwd).  Writes
+ *   rows[B][AVR_METRICS_COLS] = per row: T60 of ori, pred (seconds; NaN
+ *     where the -25 dB sample is not after the -5 dB one or the decay slope
+ *     is 0), EDT of ori, pred (seconds), C50 of ori, pred (dB), then the
+ *     row's sums over the n FFT bins / samples of the Angle, Amplitude and
+ *     Envelope terms;
+ *   means[7] = Angle, Amplitude, Envelope, T60, EDT, C50 errors and the
+ *     3-resolution MR-STFT (fft 512/256/128), metric_cal's first seven
+ *     results, rows reduced in order;
+ *   ori_energy, pred_energy [B][n] = the normalised energy decay curves (dB).
+ * The workspace holds avr_metrics_workspace bytes.  Bad arguments are
+ * refused before any device call. */
+#define AVR_METRICS_COLS 9
+int avr_metrics_workspace(int32_t B, int32_t n, int64_t* bytes);
+int avr_metrics(int32_t B, int32_t n, double fs, int32_t s50, int32_t window, const float* ori,
+                const float* pred, const float* ir_twiddle, const float* win_table,
+                const float* tw512, float* rows, float* means, float* ori_energy,
+                float* pred_energy, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- training-loop gradient post-processing (avr_runner.py:190-196) -----
  * For each of n_tensors fp32 gradients (HOST arrays of device pointers and
  * element counts): g = isfinite(g * coef) ? g * coef : 0, where coef is a
