@@ -5,11 +5,18 @@ Encodings are the HIP hash grid (`avr_amd.encoding`); the MLPs are plain
 `nn.Linear(bias=False)` stacks with ReLU (tcnn FullyFusedMLP / CutlassMLP
 have no biases), run by PyTorch-ROCm (hipBLASLt GEMMs) so autograd covers
 them.  `mlp_dtype` selects the GEMM precision (tcnn runs its MLPs in fp16;
-bf16 is the MI355X MFMA-native choice).  The channel-embedding ablations of
-AVRModel (model.py:71-181, "injection"/"concat") are outside the hot path
-and not provided.
+bf16 is the MI355X MFMA-native choice).
+
+The channel embeddings of AVRModel (model.py:11-61, 71-235; `channel_embed`
+in the model config, `ch_idx` [bs] in the call) are provided in both forms,
+for each of the three networks: "add" (`InjectionMLP`: a per-pose fp32
+embedding row added to every hidden layer's output before its ReLU, on
+`csrc/chembed.hip`) and "concat" (an embedding row appended to the network's
+input, as one more per-pose part of the grouped concatenation).
 """
 from __future__ import annotations
+
+import math
 
 import torch
 import torch.nn as nn
@@ -18,6 +25,7 @@ import torch.nn.functional as F
 import os
 
 from . import sigma as _sigma
+from .chembed import group_bias_relu
 from .concat import grouped_concat
 from .encoding import HashGridEncoding
 from .options import DEFAULT, KernelOptions, resolve
@@ -500,6 +508,62 @@ class MLP(nn.Module):
         return self.last(self.hidden(x))
 
 
+class InjectionMLP(nn.Module):
+    """The reference's LayeredTCNNWithInjection (model.py:11-61): one
+    bias-free layer per hidden layer, each followed by
+    `h = layer(x) + layer_embeddings[l][ch]; x = relu(h)`, and a plain output
+    layer.  The layer output is the MLP dtype's (tcnn's 16-bit output), the
+    embedding fp32, so the sum and the ReLU run in fp32 and the next layer's
+    input is rounded again: x = round(relu(float(y) + e)).
+
+    `ch` is one channel index per group of `rows_per_group` consecutive rows
+    (a pose's samples).  Each injected layer is the GEMM `_Linear` and
+    `chembed.group_bias_relu` (csrc/chembed.hip, or the torch ops on the CPU,
+    with KernelOptions(chembed=False) and for shapes the kernel refuses).
+    With ch=None the add is skipped, as in the reference, and the network is
+    `MLP` with the same weights."""
+
+    def __init__(self, n_in, n_out, cfg, ch_num, dtype=torch.float32, options=None):
+        super().__init__()
+        self.options = resolve(options)
+        width = int(cfg["n_neurons"])
+        depth = int(cfg["n_hidden_layers"])
+        if cfg.get("activation", "ReLU") != "ReLU":
+            raise ValueError("only ReLU MLPs are used by the reference configs")
+        dims = [n_in] + [width] * depth
+        self.hidden_layers = nn.ModuleList(nn.Linear(a, b, bias=False) for a, b in zip(dims[:-1], dims[1:]))
+        self.layer_embeddings = nn.ParameterList(
+            nn.Parameter(torch.randn(int(ch_num), width) / math.sqrt(width)) for _ in range(depth))
+        self.output_layer = nn.Linear(dims[-1], n_out, bias=False)
+        self.dtype = dtype
+        self.n_output_dims = n_out
+
+    @property
+    def layers(self):
+        """Hidden layers then the output layer, as `MLP.layers` holds them."""
+        return list(self.hidden_layers) + [self.output_layer]
+
+    def hidden(self, x, ch=None, rows_per_group=None, link=None):
+        """The last hidden activation (what the output layer, or the fused
+        head, is applied to)."""
+        if ch is None:
+            return MLP._chain(self, x, list(self.hidden_layers), link)
+        if rows_per_group is None:
+            rows_per_group = x.size(0) // ch.numel()
+        ch = ch.reshape(-1).to(device=x.device, dtype=torch.int64)
+        x = x.to(self.dtype).contiguous()
+        cache = not torch.is_grad_enabled()
+        for lin, emb in zip(self.hidden_layers, self.layer_embeddings):
+            y = _Linear.apply(x, lin.weight, self.dtype, cache, self.options)
+            x = group_bias_relu(y, emb, ch, rows_per_group, self.options)
+        return x
+
+    last = MLP.last
+
+    def forward(self, x, ch=None, rows_per_group=None):
+        return self.last(self.hidden(x, ch, rows_per_group))
+
+
 class _Broadcast(torch.autograd.Function):
     """e [G, E] -> [B, R, S, E] broadcast over each group's rows; the backward
     sums the group's row gradients in fp32 (autograd's own expand backward
@@ -628,9 +692,16 @@ def _cat_features(parts, layout):
     return torch.cat(parts, -1).view(-1, sum(p.size(-1) for p in parts))
 
 
+def _embed_rows(table, ch, n):
+    """table[ch] [bs, E] expanded over each pose's n rows: [bs * n, E]."""
+    return table[ch].unsqueeze(1).expand(-1, n, -1).reshape(ch.numel() * n, table.size(1))
+
+
 class AVRModel(nn.Module):
-    """model.py:63-235 without channel embedding: pos/dir/tx hash grids,
-    sigma encoder (-> 128) and decoder (-> 1), signal network (-> T).
+    """model.py:63-235: pos/dir/tx hash grids, sigma encoder (-> 128) and
+    decoder (-> 1), signal network (-> T), each network optionally with a
+    channel embedding (`cfg["channel_embed"]`, model.py:71-89: "add" makes it
+    an `InjectionMLP`, "concat" widens its input by an embedding row).
     `options`: the kernel selection (avr_amd.KernelOptions; defaults are the
     shipped paths)."""
 
@@ -641,11 +712,50 @@ class AVRModel(nn.Module):
         self._dir_encoding = HashGridEncoding(3, cfg["dir_encoding_sig"], dtype=enc_dtype, seed=2, options=o)
         self._tx_encoding = HashGridEncoding(3, cfg["tx_encoding_sig"], dtype=enc_dtype, seed=3, options=o)
         self.signal_output_dim = int(cfg["signal_output_dim"])
-        self._model_encoder_sigma = MLP(self._pos_encoding.n_output_dims, 128,
-                                        cfg["sigma_encoder_network"], mlp_dtype, o)
-        self._model_decoder_sigma = MLP(128, 1, cfg["sigma_decoder_network"], mlp_dtype, o)
+
+        # model.py:71-89: six flags; a block without connection_type, or with
+        # is_embed false, activates nothing and ch_idx is then ignored
+        ch = cfg.get("channel_embed") or {}
+        is_embed = bool(ch.get("is_embed", False))
+        conn = ch.get("connection_type", None)
+        self.ch_num = int(ch.get("ch_num", 0))
+        dims = {"enc": int(ch.get("emb_dim_sigma_encoder", 0)), "dec": int(ch.get("emb_dim_sigma_decoder", 0)),
+                "sig": int(ch.get("emb_dim_signal_network", 0))}
+        flags = {"enc": bool(ch.get("is_sigma_encoder", False)), "dec": bool(ch.get("is_sigma_decoder", False)),
+                 "sig": bool(ch.get("is_signal_network", False))}
+        self.enc_injection, self.dec_injection, self.sig_injection = (
+            is_embed and conn == "add" and flags[k] for k in ("enc", "dec", "sig"))
+        self.enc_concat, self.dec_concat, self.sig_concat = (
+            is_embed and conn == "concat" and flags[k] for k in ("enc", "dec", "sig"))
+        self.emb_dim_enc, self.emb_dim_dec, self.emb_dim_sig = dims["enc"], dims["dec"], dims["sig"]
+
+        def network(n_in, n_out, net_cfg, inject, concat, emb_name, emb_dim):
+            # parameters are registered in the reference's order: a concat
+            # embedding before its network (model.py:109-121)
+            if inject:
+                return InjectionMLP(n_in, n_out, net_cfg, self.ch_num, mlp_dtype, o)
+            if concat:
+                # (an embedding of width 0 is an empty tensor, as in the reference)
+                setattr(self, emb_name, nn.Parameter(
+                    torch.randn(self.ch_num, emb_dim) / (math.sqrt(emb_dim) if emb_dim else 1.0)))
+                n_in += emb_dim
+            return MLP(n_in, n_out, net_cfg, mlp_dtype, o)
+
+        self._model_encoder_sigma = network(self._pos_encoding.n_output_dims, 128, cfg["sigma_encoder_network"],
+                                            self.enc_injection, self.enc_concat, "encoder_channel_embedding",
+                                            self.emb_dim_enc)
+        self._model_decoder_sigma = network(128, 1, cfg["sigma_decoder_network"], self.dec_injection,
+                                            self.dec_concat, "decoder_channel_embedding", self.emb_dim_dec)
         sig_in = 128 + self._dir_encoding.n_output_dims + self._tx_encoding.n_output_dims
-        self._model_signal = MLP(sig_in, self.signal_output_dim, cfg["signal_network"], mlp_dtype, o)
+        self._model_signal = network(sig_in, self.signal_output_dim, cfg["signal_network"], self.sig_injection,
+                                     self.sig_concat, "signal_channel_embedding", self.emb_dim_sig)
+        self.encoder_mode, self.decoder_mode, self.signal_mode = (
+            "injection" if i else "concat" if c else "none"
+            for i, c in ((self.enc_injection, self.enc_concat), (self.dec_injection, self.dec_concat),
+                         (self.sig_injection, self.sig_concat)))
+        # any embedding: the fused sigma / h1 inference kernels (csrc/sigma.hip)
+        # implement the plain networks only and are never taken
+        self._has_embed = (self.encoder_mode, self.decoder_mode, self.signal_mode) != ("none",) * 3
         self._sigma_pack = _sigma.SigmaWeights()
 
     # AVRRender passes ray_layout=(B, R, S) to networks that declare this
@@ -657,29 +767,80 @@ class AVRModel(nn.Module):
     # torch's RNG prologue (avr_amd.graph)
     draws_no_device_rng = True
 
+    def _channel(self, pts, ch_idx):
+        """ch_idx [bs] (int64 or int32) as the int64 device tensor the
+        embedding paths index with; None for a model with no active mode
+        (the reference ignores the index there)."""
+        if not self._has_embed:
+            return None
+        if ch_idx is None:
+            if "concat" in (self.encoder_mode, self.decoder_mode, self.signal_mode):
+                raise ValueError("AVRModel: a 'concat' channel embedding needs ch_idx (its networks' inputs "
+                                 "include the embedding row)")
+            return None
+        ch = torch.as_tensor(ch_idx, device=pts.device).reshape(-1).to(torch.int64)
+        if ch.numel() != pts.size(0):
+            raise ValueError(f"AVRModel: ch_idx has {ch.numel()} entries for a batch of {pts.size(0)}")
+        return ch
+
+    @staticmethod
+    def _append_embedding(x, table, ch, n, L, dtype, grouped):
+        """The input of a "concat" network: x [N, K] and each pose's
+        embedding row, in the network's dtype.  With the renderer's layout the
+        row is one more per-pose part of `avr_concat_fwd` (its gradient summed
+        per pose in fp32, in a fixed order); otherwise the rows are expanded
+        and concatenated by torch (the reference's own ops)."""
+        E = table.size(1)
+        if grouped and E >= 8 and E % 8 == 0 and x.size(1) % 8 == 0 and x.size(1) + E <= 512:
+            return grouped_concat([(x, 1), (table[ch], n)], x.size(0), dtype, splits=[1, L[1]])
+        return torch.cat([x.to(dtype), _embed_rows(table, ch, n).to(dtype)], -1)
+
     def _trunk(self, pts, view, tx, ch_idx, ray_layout):
         """Everything up to the signal network's input: (attn, features)."""
-        if ch_idx is not None:
-            raise NotImplementedError("channel-embedding variants are not provided")
+        ch = self._channel(pts, ch_idx)
         bs, n = pts.size(0), pts.size(1)
+        N = bs * n
         L = ray_layout
-        if _fused_sigma_ok(self, pts, L, _sigma.MESHRIR):
+        if not self._has_embed and _fused_sigma_ok(self, pts, L, _sigma.MESHRIR):
             return self._trunk_fused(pts, view, tx, L)
+        grouped = _concat_ok(pts, L, self.options)
+        enc, dec = self._model_encoder_sigma, self._model_decoder_sigma
         pos_enc = self._pos_encoding(_unit(pts.reshape(-1, 3)))
-        sigma_feat = self._model_encoder_sigma(pos_enc)
-        attn = self._model_decoder_sigma(F.relu(sigma_feat))
-        if _concat_ok(pts, L, self.options):
+        if self.enc_injection:
+            sigma_feat = enc(pos_enc, ch, n)
+        elif self.enc_concat:
+            sigma_feat = enc(self._append_embedding(pos_enc, self.encoder_channel_embedding, ch, n, L, enc.dtype,
+                                                    grouped))
+        else:
+            sigma_feat = enc(pos_enc)
+        dec_in = F.relu(sigma_feat)
+        if self.dec_injection:
+            attn = dec(dec_in, ch, n)
+        elif self.dec_concat:
+            attn = dec(self._append_embedding(dec_in, self.decoder_channel_embedding, ch, n, L, dec.dtype, grouped))
+        else:
+            attn = dec(dec_in)
+        if grouped:
             B, R, S = L
             dir_e = self._dir_encoding(_unit(_per_ray(view.reshape(-1, 3), L)))
             tx_e = self._tx_encoding(_unit(_per_pose(tx.reshape(-1, 3), L)))
-            base = grouped_concat([(sigma_feat, 1), (dir_e, S), (tx_e, R * S)], bs * n, sigma_feat.dtype,
-                                  splits=[1, 1, R])
+            parts = [(sigma_feat, 1), (dir_e, S), (tx_e, R * S)]
+            E = self.emb_dim_sig
+            if self.sig_concat and E >= 8 and E % 8 == 0 and sum(p.size(1) for p, _ in parts) + E <= 512:
+                base = grouped_concat(parts + [(self.signal_channel_embedding[ch], R * S)], N, sigma_feat.dtype,
+                                      splits=[1, 1, R, R])
+            else:
+                base = grouped_concat(parts, N, sigma_feat.dtype, splits=[1, 1, R])
+                if self.sig_concat:
+                    base = torch.cat([base, _embed_rows(self.signal_channel_embedding, ch, n).to(base.dtype)], -1)
             return torch.abs(F.leaky_relu(attn)).view(bs, n, 1), base
         dir_enc = _grouped(self._dir_encoding, _unit(view.reshape(-1, 3)), L, "ray")
         tx_enc = _grouped(self._tx_encoding, _unit(tx.reshape(-1, 3)), L, "pose")
         dt = sigma_feat.dtype
         sf = sigma_feat if L is None else sigma_feat.view(*L, -1)
         base = _cat_features([sf, dir_enc.to(dt), tx_enc.to(dt)], L)
+        if self.sig_concat:
+            base = torch.cat([base, _embed_rows(self.signal_channel_embedding, ch, n).to(dt)], -1)
         attn = torch.abs(F.leaky_relu(attn)).view(bs, n, 1)
         return attn, base
 
@@ -723,11 +884,13 @@ class AVRModel(nn.Module):
 
     def _signal_hidden(self, pts, view, tx, ch_idx, ray_layout):
         """(attn, h): h the signal network's last hidden activation."""
-        if (ch_idx is None and _fused_sigma_ok(self, pts, ray_layout, _sigma.MESHRIR)
+        if (not self._has_embed and _fused_sigma_ok(self, pts, ray_layout, _sigma.MESHRIR)
                 and self.options.fused_h1 and _sigma.h1_ok(self)):
             attn, h1 = self._trunk_fused_h1(pts, view, tx, ray_layout)
             return attn, self._model_signal.hidden_from(h1, 1)
         attn, base = self._trunk(pts, view, tx, ch_idx, ray_layout)
+        if self.sig_injection:
+            return attn, self._model_signal.hidden(base, self._channel(pts, ch_idx), pts.size(1))
         return attn, self._model_signal.hidden(base)
 
     def forward(self, pts, view, tx, ch_idx=None, ray_layout=None):

@@ -42,6 +42,9 @@ class KernelOptions:
     narrow: str = "80"
     # training: one-output layers on avr_linear_out1_* (one pass over x)
     out1: bool = True
+    # channel-embedding "add" layers: the per-pose bias + ReLU and its
+    # backward on csrc/chembed.hip; False runs the torch-op composition
+    chembed: bool = True
     # the shipped TunableOp solutions for the file's GEMM shapes
     tunableop: bool = True
     # weight gradients split over rows only for weights with at least this

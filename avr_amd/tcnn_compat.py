@@ -16,7 +16,18 @@ saves them under `network_fn.<module>.params`.  Here:
   `mlp_to_tcnn` / `mlp_from_tcnn` convert one network; `to_reference` /
   `from_reference` convert whole state dicts, so a checkpoint written by the
   reference loads into `avr_amd` models and vice versa
-  (`TrainStep.load_checkpoint` detects the layout).
+  (`TrainStep.load_checkpoint` detects the layout);
+* an `InjectionMLP` (the reference's LayeredTCNNWithInjection, model.py:11-61)
+  is one tcnn network PER LAYER, each with `n_hidden_layers` 0: a single
+  matrix with both its input and its output width padded to 16, under
+  `<mlp>.hidden_layers.{i}.params` and `<mlp>.output_layer.params`.  The
+  fp32 embeddings (`<mlp>.layer_embeddings.{i}`, and the concat models'
+  `*_channel_embedding`) are plain parameters with the reference's names
+  and carry over by key.  A concat model's first layer is
+  pad16(n_in + emb_dim) wide.  Adam state of an `InjectionMLP` is not
+  re-laid out (its layers stay unpadded): such a checkpoint restores here,
+  and the reference's state for one restarts the optimiser with the
+  `RuntimeWarning` of `TrainStep.load_checkpoint`.
 
 Parity unpinned: tinycudann is not in /root/reference and no reference
 checkpoint exists, so the matrix order above is restated from upstream
@@ -27,7 +38,7 @@ from __future__ import annotations
 
 import torch
 
-from .model import MLP
+from .model import MLP, InjectionMLP
 
 _ALIGN = 16  # tcnn's tensor-core width: input / output padding
 
@@ -83,23 +94,62 @@ def _mlps(module):
     return {name: m for name, m in module.named_modules() if isinstance(m, MLP)}
 
 
+def _injection_layers(module):
+    """{state-dict prefix: nn.Linear} of every InjectionMLP layer, each its
+    own tcnn network in the reference: `<mlp>.hidden_layers.{i}.` and
+    `<mlp>.output_layer.`."""
+    out = {}
+    for name, m in module.named_modules():
+        if isinstance(m, InjectionMLP):
+            pre = name + "." if name else ""
+            for i, lin in enumerate(m.hidden_layers):
+                out[f"{pre}hidden_layers.{i}."] = lin
+            out[pre + "output_layer."] = m.output_layer
+    return out
+
+
+def linear_to_tcnn(lin) -> torch.Tensor:
+    """One bias-free layer as the flat `params` of a tcnn network without
+    hidden layers: [pad16(out)][pad16(in)], padding zero."""
+    w = lin.weight.detach().float()
+    m = torch.zeros(_pad(w.size(0)), _pad(w.size(1)), dtype=torch.float32, device=w.device)
+    m[:w.size(0), :w.size(1)] = w
+    return m.reshape(-1)
+
+
+def linear_from_tcnn(lin, params: torch.Tensor, key: str = "params") -> None:
+    """Load `linear_to_tcnn`'s layout into the layer (in place)."""
+    out, inp = lin.weight.shape
+    params = params.detach().reshape(-1)
+    if params.numel() != _pad(out) * _pad(inp):
+        raise ValueError(f"tcnn {key}: {params.numel()} values, this layer needs {_pad(out) * _pad(inp)} "
+                         f"(weight {(out, inp)}, both widths padded to {_ALIGN})")
+    with torch.no_grad():
+        lin.weight.copy_(params.view(_pad(out), _pad(inp))[:out, :inp].to(lin.weight))
+
+
 def to_reference(module) -> dict:
     """`module.state_dict()` with every MLP's per-layer weights replaced by
-    tcnn's flat `<mlp>.params` (what the reference's modules hold)."""
+    tcnn's flat `<mlp>.params` (what the reference's modules hold), and every
+    InjectionMLP layer's weight by that layer's own `params`."""
     sd = module.state_dict()
     for name, mlp in _mlps(module).items():
         pre = name + "." if name else ""
         for k in [k for k in sd if k.startswith(pre + "layers.")]:
             del sd[k]
         sd[pre + "params"] = mlp_to_tcnn(mlp).to(next(iter(mlp.parameters())).device)
+    for pre, lin in _injection_layers(module).items():
+        del sd[pre + "weight"]
+        sd[pre + "params"] = linear_to_tcnn(lin)
     return sd
 
 
 def is_reference_layout(module, state_dict) -> bool:
     """True when the state dict holds tcnn-style `<mlp>.params` for the
     module's MLPs (a checkpoint written by the reference)."""
-    names = list(_mlps(module))
-    return bool(names) and all(((n + ".") if n else "") + "params" in state_dict for n in names)
+    keys = [((n + ".") if n else "") + "params" for n in _mlps(module)]
+    keys += [pre + "params" for pre in _injection_layers(module)]
+    return bool(keys) and all(k in state_dict for k in keys)
 
 
 def from_reference(module, state_dict, strict: bool = True):
@@ -114,11 +164,19 @@ def from_reference(module, state_dict, strict: bool = True):
                 raise KeyError(f"reference state dict has no {key!r}")
             continue
         mlp_from_tcnn(mlp, sd.pop(key))
+    injected = _injection_layers(module)
+    for pre, lin in injected.items():
+        if pre + "params" not in sd:
+            if strict:
+                raise KeyError(f"reference state dict has no {pre + 'params'!r}")
+            continue
+        linear_from_tcnn(lin, sd.pop(pre + "params"), pre + "params")
     own = module.state_dict()
     rest = {k: v for k, v in sd.items() if k in own}
     unexpected = [k for k in sd if k not in own]
     missing = [k for k in own if k not in rest and not any(
-        k.startswith(((n + ".") if n else "") + "layers.") for n in mlps)]
+        k.startswith(((n + ".") if n else "") + "layers.") for n in mlps)
+        and not any(k == pre + "weight" for pre in injected)]
     if strict and (unexpected or missing):
         raise KeyError(f"reference state dict: unexpected {unexpected}, missing {missing}")
     module.load_state_dict(rest, strict=False)

@@ -619,6 +619,37 @@ int avr_adam_step(int32_t n_tensors, float* const* params, const float* const* g
                   const float* step_size, const float* bc2_sqrt, double beta1, double beta2,
                   float eps, float weight_decay, const float* coef, void* stream);
 
+/* ---- channel-embedding injection: per-group bias + ReLU (csrc/chembed.hip) --
+ * The reference's LayeredTCNNWithInjection step (model.py:55-61):
+ *   out[r][:] = round_dtype(relu(float(y[r][:]) + table[idx[r / rows_per_group]][:]))
+ * for y, out [N][W] of `dtype` (AVR_DTYPE_F32 / F16 / BF16), table [C][W]
+ * fp32 and idx [N / rows_per_group] int64, all on the device.  ReLU is
+ * torch's (NaN stays NaN, +inf stays).  A group whose index is outside
+ * [0, C) reads nothing from the table and its rows become NaN.
+ *
+ * avr_group_bias_relu_bwd reads gy and the saved out and writes
+ *   g[r][:] = out[r][:] <= 0 ? 0 : gy[r][:]       (threshold_backward, in dtype)
+ *   g_table[c][:] = sum of g over the rows of every group with idx == c  (fp32)
+ * in two launches without atomics: fp32 column sums per chunk of a group's
+ * rows into `workspace` (avr_group_bias_relu_workspace bytes), then one sum
+ * per g_table element over the chunks in a fixed order (groups ascending,
+ * chunks ascending).  Every g_table element is stored, never accumulated: a
+ * channel no group names gets zeros, out-of-range groups add nothing, and the
+ * result is the same bits from run to run.
+ *
+ * Shapes: 1 <= N < 2^31, rows_per_group divides N, W a multiple of 8 in
+ * [8, 1024], 1 <= C <= 65535; y, out, gy, g and table 16-byte aligned.
+ * Element offsets are 64-bit (N * W may pass 2^31).  No call synchronises
+ * or copies to the host, so all of them can be captured into a graph.  Bad
+ * arguments are refused (AVR_E_ARG) before any device call. */
+int avr_group_bias_relu_fwd(int64_t N, int32_t W, int64_t rows_per_group, int32_t C, const void* y,
+                            int32_t dtype, const float* table, const int64_t* idx, void* out,
+                            void* stream);
+int avr_group_bias_relu_workspace(int64_t N, int32_t W, int64_t rows_per_group, int64_t* bytes);
+int avr_group_bias_relu_bwd(int64_t N, int32_t W, int64_t rows_per_group, int32_t C, const void* gy,
+                            const void* out, int32_t dtype, const int64_t* idx, void* g,
+                            void* workspace, int64_t workspace_bytes, float* g_table, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
