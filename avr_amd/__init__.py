@@ -19,6 +19,17 @@ from .metrics import (  # noqa: F401
     metric_cal,
     metric_rows,
 )
+from .auralize import (  # noqa: F401
+    auralize_dump,
+    butter_bandpass_sos,
+    convolve_source,
+    seg_hop_samples,
+    sliding_frames,
+    sosfilt_zi,
+    synth_observation,
+    white_noise,
+    zero_phase_sos,
+)
 from .options import KernelOptions  # noqa: F401
 from . import workloads  # noqa: F401
 

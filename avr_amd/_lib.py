@@ -178,6 +178,10 @@ _SIGS = {
     "avr_group_bias_relu_workspace": (ctypes.c_int, [_c_i64, _c_i32, _c_i64, _vp]),
     "avr_group_bias_relu_bwd": (ctypes.c_int, [_c_i64, _c_i32, _c_i64, _c_i32, _vp, _vp, _c_i32, _vp, _vp, _vp,
                                                _c_i64, _vp, _vp]),
+    "avr_conv_source": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, _c_i64, _vp, _vp, _vp, _vp]),
+    "avr_sosfiltfilt_workspace": (ctypes.c_int, [_c_i64, _c_i64, _c_i32, _c_i32, _vp]),
+    "avr_sosfiltfilt": (ctypes.c_int, [_c_i64, _c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _c_i32, _vp, _c_i32,
+                                       _vp, _c_i64, _vp]),
     "avr_sigma_pack_bytes": (ctypes.c_int, [_c_i32, _vp]),
     "avr_sigma_desc_size": (ctypes.c_int, []),
     "avr_sigma_fwd": (ctypes.c_int, [_vp] * 3 + [_c_i32, _vp, _vp]),

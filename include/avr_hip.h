@@ -650,6 +650,36 @@ int avr_group_bias_relu_bwd(int64_t N, int32_t W, int64_t rows_per_group, int32_
                             const void* out, int32_t dtype, const int64_t* idx, void* g,
                             void* workspace, int64_t workspace_bytes, float* g_table, void* stream);
 
+/* ---- auralization (whitenoise_bandpass_doa.py:93-117) --------------------
+ * The reference's DoA evaluation chain in front of its estimators.
+ *
+ * avr_conv_source: y[s][c][:] = np.convolve(x[s], h[c], "full") for h [C][Nh],
+ *   x [S][L], y [S][C][L + Nh - 1], fp32, on the exact-fp32 MFMA: every
+ *   output is one fp32 FMA chain in ascending tap order, so the result is the
+ *   same bits from run to run and a channel's row does not depend on which
+ *   other channels or sources share the call.  Any S, C, Nh, L >= 1 (L < Nh
+ *   included); element offsets are 64-bit.
+ *
+ * avr_sosfiltfilt: scipy.signal.sosfiltfilt(sos, y, axis=-1) with its
+ *   defaults on y [rows][n] (fp32 or fp64: AVR_DTYPE_F32 / AVR_DTYPE_F64)
+ *   -> out [rows][n] (fp64, or fp32 = the fp64 result rounded).  sos is a
+ *   DEVICE table [n_sections][6] of doubles with a0 == 1, zi a DEVICE table
+ *   [n_sections][2] = sosfilt_zi(sos); padlen is scipy's 3 * ntaps and
+ *   n > padlen is required; 1 <= n_sections <= 8.  The recurrence is direct
+ *   form II transposed in fp64, one thread per row.  The workspace holds
+ *   avr_sosfiltfilt_workspace bytes (the forward pass over the extended rows).
+ *
+ * No call synchronises or copies to the host.  Bad arguments are refused
+ * (AVR_E_ARG) before any device call. */
+#define AVR_DTYPE_F64 3
+int avr_conv_source(int32_t S, int32_t C, int32_t Nh, int64_t L, const float* h, const float* x,
+                    float* y, void* stream);
+int avr_sosfiltfilt_workspace(int64_t rows, int64_t n, int32_t n_sections, int32_t padlen,
+                              int64_t* bytes);
+int avr_sosfiltfilt(int64_t rows, int64_t n, int32_t n_sections, int32_t padlen, const double* sos,
+                    const double* zi, const void* y, int32_t in_dtype, void* out, int32_t out_dtype,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
