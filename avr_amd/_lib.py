@@ -20,6 +20,7 @@ DTYPE_F32 = 0
 DTYPE_F16 = 1
 DTYPE_BF16 = 2
 MAX_AZI = 512  # AVR_MAX_AZI
+IRFFT_MAX_N = 13476  # AVR_IRFFT_MAX_N: longest IR of avr_irfft / avr_irfft_bwd
 
 _c_i32 = ctypes.c_int32
 _c_i64 = ctypes.c_int64

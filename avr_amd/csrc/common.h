@@ -34,6 +34,12 @@ int device_cus();
 // (spec2 -> ir2, may be null) in the same launch (render_fwd.hip).
 int launch_irfft(int B, int F, const float* spec, const float* spec2, const float* tw, float* ir,
                  float* ir2, void* stream);
+// The one length limit of avr_irfft and avr_irfft_bwd (AVR_IRFFT_MAX_N): the
+// largest even n whose LDS, dynamic plus static, fits a CU's 160 KiB in both
+// kernels.  Checked before any launch by every entry point that transforms.
+constexpr int kIrfftMaxN = AVR_IRFFT_MAX_N;
+constexpr size_t kLdsPerCu = 160 * 1024;
+#define AVR_IRFFT_LIMIT_TEXT "irfft length n > 13476 not supported (n*12 B of twiddles and data must fit the 160 KiB LDS)"
 
 // MR-STFT of the criterion's resolutions 0-2 on two batches of IRs [B][n]
 // (criterion.hip), the validation metrics' multi_stft: *out (device) = the

@@ -695,6 +695,9 @@ extern "C" int avr_criterion_bwd(int32_t B, int32_t F, const float* weights, con
                        grad_pred_time, W);
     if (int e = check_launch("crit_bwd_time_kernel")) return e;
     const size_t lds = (size_t)P.n * 3 * sizeof(float);
+    if (lds > 65536)  // n >= 5462; make_plan's n <= 12288 keeps it (plus 2112 B static) inside 160 KiB
+        (void)hipFuncSetAttribute((const void*)crit_bwd_spec_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds);
     hipLaunchKernelGGL(crit_bwd_spec_kernel, dim3((F + 31) / 32, B), dim3(kThreads), lds,
                        as_stream(stream), P, reinterpret_cast<const float2*>(pred),
                        reinterpret_cast<const float2*>(ori),

@@ -666,12 +666,24 @@ __global__ __launch_bounds__(256) void spectrum_finalize_kernel(int B, int P, in
 // latency), then the 8 slices are combined in LDS in a fixed order.
 // Rows b >= B1 come from (spec2, ir2): the criterion transforms the
 // predicted and measured spectra in one launch.
+constexpr int kIrfftRedRows = 8;  // bin / t slices combined through LDS by both transforms
+// dynamic + static LDS of the two transforms at length n
+constexpr size_t irfft_lds(int n) { return (size_t)(n / 2 + 1 + n) * sizeof(float2); }
+constexpr size_t irfft_bwd_lds(int n) { return (size_t)n * (sizeof(float2) + sizeof(float)); }
+constexpr size_t kIrfftStatic = kIrfftRedRows * 33 * sizeof(float);
+constexpr size_t kIrfftBwdStatic = kIrfftRedRows * 33 * sizeof(float2);
+static_assert(irfft_lds(kIrfftMaxN) + kIrfftStatic <= kLdsPerCu &&
+                  irfft_bwd_lds(kIrfftMaxN) + kIrfftBwdStatic <= kLdsPerCu,
+              "AVR_IRFFT_MAX_N must launch in both transforms");
+static_assert(kIrfftMaxN % 2 == 0 && irfft_bwd_lds(kIrfftMaxN + 2) + kIrfftBwdStatic > kLdsPerCu,
+              "AVR_IRFFT_MAX_N is the largest even length that launches in both");
+
 __global__ __launch_bounds__(256) void irfft_kernel(int F, int B1, const float2* __restrict__ spec,
                                                     const float2* __restrict__ spec2,
                                                     const float2* __restrict__ twg,
                                                     float* __restrict__ ir, float* __restrict__ ir2) {
     extern __shared__ float2 lds[];
-    __shared__ float red[8][33];
+    __shared__ float red[kIrfftRedRows][33];
     const int n = 2 * (F - 1);
     float2* X = lds;       // [F]
     float2* tw = lds + F;  // [n]
@@ -732,7 +744,7 @@ __global__ __launch_bounds__(256) void irfft_bwd_kernel(int F, const float* __re
                                                         const float2* __restrict__ twg,
                                                         float2* __restrict__ grad) {
     extern __shared__ float lds_irb[];
-    __shared__ float2 red[8][33];
+    __shared__ float2 red[kIrfftRedRows][33];
     const int n = 2 * (F - 1);
     const int b = blockIdx.y;
     float2* tw = reinterpret_cast<float2*>(lds_irb);  // [n]
@@ -1132,9 +1144,12 @@ int launch_irfft(int B, int F, const float* spec, const float* spec2, const floa
                  float* ir2, void* stream) {
     AVR_REQUIRE(B >= 1 && F >= 2 && spec && tw && ir, "avr_irfft: bad args");
     const int n = 2 * (F - 1);
-    AVR_REQUIRE(n <= 16384, "avr_irfft: n too large");
-    const size_t lds = (size_t)(F + n) * sizeof(float2);
+    AVR_REQUIRE(n <= kIrfftMaxN, "avr_irfft: " AVR_IRFFT_LIMIT_TEXT);
+    const size_t lds = irfft_lds(n);
     const int rows = spec2 ? 2 * B : B;
+    if (lds > 65536)
+        (void)hipFuncSetAttribute((const void*)irfft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds);
     hipLaunchKernelGGL(irfft_kernel, dim3((n + 31) / 32, rows), dim3(256), lds, as_stream(stream),
                        (int)F, (int)B, reinterpret_cast<const float2*>(spec),
                        reinterpret_cast<const float2*>(spec2 ? spec2 : spec),
@@ -1152,8 +1167,8 @@ extern "C" int avr_irfft_bwd(int32_t B, int32_t F, const float* grad_ir, const f
                              float* grad_spec, void* stream) {
     AVR_REQUIRE(B >= 1 && F >= 2 && grad_ir && tw && grad_spec, "avr_irfft_bwd: bad args");
     const int n = 2 * (F - 1);
-    const size_t lds = (size_t)n * (sizeof(float2) + sizeof(float));
-    AVR_REQUIRE(lds <= 160 * 1024, "avr_irfft_bwd: n too large for LDS");
+    AVR_REQUIRE(n <= kIrfftMaxN, "avr_irfft_bwd: " AVR_IRFFT_LIMIT_TEXT);
+    const size_t lds = irfft_bwd_lds(n);
     if (lds > 65536)
         (void)hipFuncSetAttribute((const void*)irfft_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds);
@@ -1231,6 +1246,8 @@ extern "C" int avr_render_core_fwd(const avr_render_params* p, int32_t B, const 
                                    void* ev_end, void* stream) {
     if (int e = validate(p)) return e;
     AVR_REQUIRE(tab && workspace && out, "avr_render_core_fwd: null pointer");
+    // the IR's length limit, before any kernel of the core runs
+    AVR_REQUIRE(!ir || 2 * (p->T / 2) <= kIrfftMaxN, "avr_render_core_fwd: " AVR_IRFFT_LIMIT_TEXT);
     const CoreLayout L = core_layout(p, B, sig_dtype);
     AVR_REQUIRE(workspace_bytes >= L.bytes, "avr_render_core_fwd: workspace too small");
     char* ws = reinterpret_cast<char*>(workspace);

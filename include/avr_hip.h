@@ -181,7 +181,12 @@ int avr_spectrum_finalize(int32_t B, int32_t P, int32_t F, const float* spart, f
                           void* stream);
 
 /* ---- a13: IR synthesis, torch.fft.irfft (utils/criterion.py:71) --------
- * spec[B][F][2] -> ir[B][n], n = 2*(F-1), tw = avr_ir_twiddle(n). */
+ * spec[B][F][2] -> ir[B][n], n = 2*(F-1), tw = avr_ir_twiddle(n).
+ * Both transforms stage their twiddles and one row in the CU's 160 KiB LDS
+ * (12 bytes per sample plus up to 2112 B of reduction scratch), so they take
+ * n <= AVR_IRFFT_MAX_N and refuse a longer one with AVR_E_ARG before any
+ * launch; so do avr_render_core_fwd with ir != NULL and avr_criterion_fwd2. */
+#define AVR_IRFFT_MAX_N 13476
 int avr_irfft(int32_t B, int32_t F, const float* spec, const float* tw, float* ir,
               void* stream);
 /* Adjoint of avr_irfft (torch's irfft backward: 1/n, the interior bins

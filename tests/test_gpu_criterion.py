@@ -63,6 +63,14 @@ def test_criterion_matches_oracle(case):
     assert err < 1e-3, (name, err)
 
 
+@pytest.mark.parametrize("F", [2732, 6145])
+def test_criterion_long_ir_matches_oracle(F):
+    """n = 5462 is the first IR whose irfft and spectrum-gradient kernels need
+    more than 64 KiB of dynamic LDS (an explicit opt-in at launch); n = 12288
+    is the criterion's longest."""
+    test_criterion_matches_oracle((f"long_{F}", 1, F, RAF_W, 30))
+
+
 def test_criterion_term_by_term_gradients():
     """Each loss term's gradient alone (the others' upstream grads zero)."""
     B, F = 2, 801

@@ -394,12 +394,22 @@ def test_nonfinite_semantics():
     assert torch.equal(_nan_render(inp, w, case.seed, None, propagate_nonfinite=True), clean)
 
 
-@pytest.mark.parametrize("F", [2, 3, 128, 512, 801, 2048])
+IR_F_MAX = _lib.IRFFT_MAX_N // 2 + 1  # largest F of avr_irfft / avr_irfft_bwd (n = 13476)
+
+
+# 2731 / 2732: either side of the 64 KiB dynamic-LDS opt-in; 8193 (n = 16384) is past the limit
+@pytest.mark.parametrize("F", [2, 3, 128, 512, 801, 2048, 2731, 2732, 4097, 5001, IR_F_MAX, 8193])
 def test_spectrum_to_ir_gradient_matches_torch_irfft(F):
     """spectrum_to_ir's backward (avr_irfft_bwd) equals torch.fft.irfft's
     autograd (utils/criterion.py:71-72: the loss is taken on the IR), DC and
-    Nyquist imaginary parts included (their gradient is zero)."""
+    Nyquist imaginary parts included (their gradient is zero).  A length past
+    AVR_IRFFT_MAX_N is refused with an error naming the limit."""
     from avr_amd import spectrum_to_ir
+
+    if F > IR_F_MAX:
+        with pytest.raises(RuntimeError, match=f"n > {_lib.IRFFT_MAX_N}"):
+            spectrum_to_ir(torch.zeros(1, F, 2, device=DEV))
+        return
 
     g = torch.Generator(device=DEV).manual_seed(F)
     B = 3
