@@ -12,6 +12,7 @@ import os
 import threading
 
 import numpy as np
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libavr_hip.so")
@@ -233,6 +234,16 @@ def load():
             raise RuntimeError("avr_amd: libavr_hip.so ABI version mismatch")
         _lib = lib
         return lib
+
+
+def _ptr(t):
+    """Device address of a tensor for a pointer argument (None stays a null pointer)."""
+    return None if t is None else t.data_ptr()
+
+
+def _stream(dev):
+    """Raw handle of torch's current stream on `dev`."""
+    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def call(name: str, *args):

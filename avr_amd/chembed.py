@@ -14,17 +14,10 @@ import ctypes
 import torch
 
 from . import _lib
+from ._lib import _ptr as _vp, _stream
 from .options import DEFAULT
 
 _CODES = {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def bias_relu_fwd(y, table, idx, rows_per_group, out=None):

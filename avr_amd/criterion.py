@@ -27,6 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._lib import _ptr, _stream
 from .renderer import _ir_twiddle
 
 LOSS_KEYS = ("spec_loss_weight", "amplitude_loss_weight", "angle_loss_weight",
@@ -37,14 +38,6 @@ _ENERGY_NFFT = 256
 
 _TABLES: dict = {}
 _TABLE_LOCK = threading.Lock()
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def _window_table(dev):

@@ -366,13 +366,8 @@ extern "C" int avr_conv_source(int32_t S, int32_t C, int32_t Nh, int64_t L, cons
     AVR_REQUIRE(nblk <= 0x7fffffffLL, "avr_conv_source: output too long");
     AVR_REQUIRE(ctiles <= 65535, "avr_conv_source: at most 65535 * 32 channels");
     const dim3 grid((unsigned)nblk, (unsigned)ctiles, (unsigned)S);
-    if (R == 16)
-        hipLaunchKernelGGL(conv_source_kernel<16>, grid, dim3(kConvThreads), 0, as_stream(stream), C, Nh, L, N,
-                           h, x, y);
-    else
-        hipLaunchKernelGGL(conv_source_kernel<32>, grid, dim3(kConvThreads), 0, as_stream(stream), C, Nh, L, N,
-                           h, x, y);
-    return check_launch("conv_source_kernel");
+    return launch("conv_source_kernel", R == 16 ? conv_source_kernel<16> : conv_source_kernel<32>, grid,
+                  dim3(kConvThreads), 0, as_stream(stream), C, Nh, L, N, h, x, y);
 }
 
 extern "C" int avr_sosfiltfilt_workspace(int64_t rows, int64_t n, int32_t n_sections, int32_t padlen,
@@ -401,10 +396,8 @@ extern "C" int avr_sosfiltfilt(int64_t rows, int64_t n, int32_t n_sections, int3
     const dim3 grid((unsigned)((rows + kSosRows - 1) / kSosRows)), block(64);
     hipStream_t st = as_stream(stream);
     switch (n_sections) {
-#define AVR_SOS_CASE(NS)                                                         \
-    case NS:                                                                     \
-        hipLaunchKernelGGL(sosfiltfilt_kernel<NS>, grid, block, 0, st, a);       \
-        break;
+#define AVR_SOS_CASE(NS) \
+    case NS: return launch("sosfiltfilt_kernel", sosfiltfilt_kernel<NS>, grid, block, 0, st, a);
         AVR_SOS_CASE(1)
         AVR_SOS_CASE(2)
         AVR_SOS_CASE(3)
@@ -415,5 +408,5 @@ extern "C" int avr_sosfiltfilt(int64_t rows, int64_t n, int32_t n_sections, int3
         AVR_SOS_CASE(8)
 #undef AVR_SOS_CASE
     }
-    return check_launch("sosfiltfilt_kernel");
+    return fail(AVR_E_ARG, "avr_sosfiltfilt: n_sections out of range");
 }

@@ -205,26 +205,6 @@ int64_t bytes_needed(int64_t N, int32_t W, int64_t rpg) {
     return (N / rpg) * chunks_per_group(rpg) * W * (int64_t)sizeof(float);
 }
 
-template <typename T>
-void launch_fwd(int64_t N, int W, int64_t rpg, int C, const void* y, const float* table, const int64_t* idx,
-                void* out, hipStream_t st) {
-    const Tile t = tile_of(W, Vec16<T>::N);
-    const int rows = (kThreads >> t.cw_log2) * kFwdIters;
-    hipLaunchKernelGGL(bias_relu_fwd_kernel<T>, dim3((unsigned)((N + rows - 1) / rows), (unsigned)t.slabs),
-                       dim3(kThreads), 0, st, (uint32_t)N, W, (uint32_t)rpg, C, t.upr, t.cw_log2,
-                       static_cast<const T*>(y), table, idx, static_cast<T*>(out));
-}
-
-template <typename T>
-void launch_bwd(int64_t N, int W, int64_t rpg, const void* gy, const void* out, void* g, float* ws,
-                hipStream_t st) {
-    const Tile t = tile_of(W, Vec16<T>::N);
-    const int64_t cpg = chunks_per_group(rpg);
-    hipLaunchKernelGGL(bias_relu_bwd_kernel<T>, dim3((unsigned)((N / rpg) * cpg), (unsigned)t.slabs),
-                       dim3(kThreads), 0, st, W, (uint32_t)rpg, (uint32_t)cpg, t.upr, t.cw_log2,
-                       static_cast<const T*>(gy), static_cast<const T*>(out), static_cast<T*>(g), ws);
-}
-
 }  // namespace
 
 extern "C" int avr_group_bias_relu_fwd(int64_t N, int32_t W, int64_t rows_per_group, int32_t C, const void* y,
@@ -237,14 +217,16 @@ extern "C" int avr_group_bias_relu_fwd(int64_t N, int32_t W, int64_t rows_per_gr
     AVR_REQUIRE(dtype_ok(dtype), "avr_group_bias_relu_fwd: unknown dtype");
     AVR_REQUIRE(aligned16(y) && aligned16(table) && aligned16(out),
                 "avr_group_bias_relu_fwd: y, table and out must be 16-byte aligned");
-    hipStream_t st = as_stream(stream);
-    if (dtype == AVR_DTYPE_F32)
-        launch_fwd<float>(N, W, rows_per_group, C, y, table, idx, out, st);
-    else if (dtype == AVR_DTYPE_F16)
-        launch_fwd<__half>(N, W, rows_per_group, C, y, table, idx, out, st);
-    else
-        launch_fwd<__hip_bfloat16>(N, W, rows_per_group, C, y, table, idx, out, st);
-    return check_launch("avr_group_bias_relu_fwd");
+    return dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16, AVR_DTYPE_BF16>(
+        dtype, "avr_group_bias_relu_fwd", [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            const Tile t = tile_of(W, Vec16<T>::N);
+            const int rows = (kThreads >> t.cw_log2) * kFwdIters;
+            return launch("avr_group_bias_relu_fwd", bias_relu_fwd_kernel<T>,
+                          dim3((unsigned)((N + rows - 1) / rows), (unsigned)t.slabs), dim3(kThreads), 0,
+                          as_stream(stream), (uint32_t)N, W, (uint32_t)rows_per_group, C, t.upr, t.cw_log2,
+                          static_cast<const T*>(y), table, idx, static_cast<T*>(out));
+        });
 }
 
 extern "C" int avr_group_bias_relu_workspace(int64_t N, int32_t W, int64_t rows_per_group, int64_t* bytes) {
@@ -271,16 +253,16 @@ extern "C" int avr_group_bias_relu_bwd(int64_t N, int32_t W, int64_t rows_per_gr
                 "avr_group_bias_relu_bwd: workspace and g_table must be 4-byte aligned");
     hipStream_t st = as_stream(stream);
     float* ws = static_cast<float*>(workspace);
-    if (dtype == AVR_DTYPE_F32)
-        launch_bwd<float>(N, W, rows_per_group, gy, out, g, ws, st);
-    else if (dtype == AVR_DTYPE_F16)
-        launch_bwd<__half>(N, W, rows_per_group, gy, out, g, ws, st);
-    else
-        launch_bwd<__hip_bfloat16>(N, W, rows_per_group, gy, out, g, ws, st);
-    if (int e = check_launch("avr_group_bias_relu_bwd")) return e;
-    const int64_t G = N / rows_per_group;
-    hipLaunchKernelGGL(table_sum_kernel, dim3((unsigned)((W + kSumCols - 1) / kSumCols), (unsigned)C),
-                       dim3(kThreads), 0, st, W, (uint32_t)G, (uint32_t)chunks_per_group(rows_per_group), idx, ws,
-                       g_table);
-    return check_launch("avr_group_bias_relu_bwd");
+    const int64_t G = N / rows_per_group, cpg = chunks_per_group(rows_per_group);
+    const char* what = "avr_group_bias_relu_bwd";
+    if (int e = dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16, AVR_DTYPE_BF16>(dtype, what, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            const Tile t = tile_of(W, Vec16<T>::N);
+            return launch(what, bias_relu_bwd_kernel<T>, dim3((unsigned)(G * cpg), (unsigned)t.slabs), dim3(kThreads),
+                          0, st, W, (uint32_t)rows_per_group, (uint32_t)cpg, t.upr, t.cw_log2,
+                          static_cast<const T*>(gy), static_cast<const T*>(out), static_cast<T*>(g), ws);
+        }))
+        return e;
+    return launch(what, table_sum_kernel, dim3((unsigned)((W + kSumCols - 1) / kSumCols), (unsigned)C),
+                  dim3(kThreads), 0, st, W, (uint32_t)G, (uint32_t)cpg, idx, ws, g_table);
 }

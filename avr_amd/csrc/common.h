@@ -12,6 +12,7 @@
 #include <type_traits>
 #include <stdint.h>
 #include <string>
+#include <utility>
 
 #include "avr_hip.h"
 
@@ -49,6 +50,54 @@ int launch_mr3(int B, int n, const float* pred_time, const float* ori_time, cons
                const float* tw512, void* ws, int64_t ws_bytes, float* out, void* stream);
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// ---------------------------------------------------------------- launches
+// Dynamic LDS a kernel may ask for without opting in through
+// hipFuncAttributeMaxDynamicSharedMemorySize.
+constexpr size_t kLdsDefault = 64 * 1024;
+
+// The one way a kernel is launched: refuses more LDS than a CU has before any
+// HIP call, opts the kernel in above the 64 KiB default (on every such launch:
+// no cache or registry), launches and returns the launch status.  A launcher
+// that issues several kernels stops at the first one refused:
+// `if (int e = launch(...)) return e;`.
+template <typename Kern, typename... Args>
+int launch(const char* what, Kern kern, dim3 grid, dim3 block, size_t lds, hipStream_t st,
+           Args&&... args) {
+    if (lds > kLdsPerCu)
+        return fail(AVR_E_CONFIG, std::string(what) + ": " + std::to_string(lds) +
+                                      " B of dynamic LDS exceed a CU's 160 KiB");
+    if (lds > kLdsDefault) {
+        const hipError_t e = hipFuncSetAttribute((const void*)kern,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess)
+            return fail((int)e, std::string(what) + ": LDS opt-in: " + hipGetErrorString(e));
+    }
+    hipLaunchKernelGGL(kern, grid, block, lds, st, std::forward<Args>(args)...);
+    return check_launch(what);
+}
+
+// ---------------------------------------------------------------- dtype dispatch
+template <int Code>
+struct dtype_tag;
+template <>
+struct dtype_tag<AVR_DTYPE_F32> { using type = float; };
+template <>
+struct dtype_tag<AVR_DTYPE_F16> { using type = __half; };
+template <>
+struct dtype_tag<AVR_DTYPE_BF16> { using type = __hip_bfloat16; };
+
+// Calls f(dtype_tag<C>{}) for the one C of Allowed that equals `code` and
+// returns its result; AVR_E_ARG for a code the entry point does not accept.
+// Only the allowed types are instantiated:
+//   dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16>(dtype, "avr_x", [&](auto tag) {
+//       using T = typename decltype(tag)::type; ... return launch(...); });
+template <int... Allowed, typename F>
+int dispatch_dtype(int code, const char* what, F&& f) {
+    int rc = 0;
+    const bool hit = ((code == Allowed ? (rc = f(dtype_tag<Allowed>{}), true) : false) || ...);
+    return hit ? rc : fail(AVR_E_ARG, std::string(what) + ": unsupported dtype");
+}
 
 // ---------------------------------------------------------------- MFMA operand hold
 // A register an MFMA reads as SrcB must not be rewritten while that MFMA may

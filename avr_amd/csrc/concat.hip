@@ -126,16 +126,12 @@ int launch_group_sum(uint32_t n_out, int div, int w8, const void* g, int g_dtype
     const uint64_t items = (uint64_t)n_out * w8;
     auto go = [&](auto kern, int J) {
         const uint64_t threads = items * J;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, n_out, div, w8, g,
-                           g_dtype, ldg, col, dst, dst_dtype);
+        return launch("avr_concat_bwd", kern, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, n_out, div,
+                      w8, g, g_dtype, ldg, col, dst, dst_dtype);
     };
-    if (div == 1)
-        go(group_sum_kernel<1>, 1);
-    else if (div <= 64)
-        go(group_sum_kernel<8>, 8);
-    else
-        go(group_sum_kernel<64>, 64);
-    return check_launch("avr_concat_bwd");
+    if (div == 1) return go(group_sum_kernel<1>, 1);
+    if (div <= 64) return go(group_sum_kernel<8>, 8);
+    return go(group_sum_kernel<64>, 64);
 }
 
 }  // namespace
@@ -167,9 +163,8 @@ extern "C" int avr_concat_fwd(int64_t N, int32_t n_src, const avr_concat_src* sr
     AVR_REQUIRE(N >= 0 && N * nch < (int64_t(1) << 31), "avr_concat_fwd: too many rows");
     if (N == 0) return 0;
     const uint64_t threads = (uint64_t)N * nch;
-    hipLaunchKernelGGL(concat_fwd_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
-                       as_stream(stream), (uint32_t)N, nch, t, out, out_dtype);
-    return check_launch("avr_concat_fwd");
+    return launch("avr_concat_fwd", concat_fwd_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
+                  as_stream(stream), (uint32_t)N, nch, t, out, out_dtype);
 }
 
 extern "C" int avr_concat_bwd(int64_t N, int32_t n_src, const avr_concat_src* src, const void* grad_out,

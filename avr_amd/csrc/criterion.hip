@@ -624,12 +624,11 @@ int launch_mr3(int B, int n, const float* pred_time, const float* ori_time, cons
     AVR_REQUIRE(ws_bytes >= W.bytes, "avr_metrics: MR-STFT workspace too small");
     AVR_REQUIRE(B <= 256, "avr_metrics: at most 256 items per call");
     // the tiles of resolutions 0..2 come first in the criterion's tile order
-    hipLaunchKernelGGL(crit_stft_kernel, dim3(P.r[kMetricRes].tile_f, B), dim3(kThreads), 0,
-                       as_stream(stream), P, pred_time, ori_time, wtab,
-                       reinterpret_cast<const float2*>(tw512), W);
-    if (int e = check_launch("crit_stft_kernel")) return e;
-    hipLaunchKernelGGL(crit_mr3_reduce_kernel, dim3(1), dim3(kRedThreads), 0, as_stream(stream), P, W, out);
-    return check_launch("crit_mr3_reduce_kernel");
+    if (int e = launch("crit_stft_kernel", crit_stft_kernel, dim3(P.r[kMetricRes].tile_f, B), dim3(kThreads), 0,
+                       as_stream(stream), P, pred_time, ori_time, wtab, reinterpret_cast<const float2*>(tw512), W))
+        return e;
+    return launch("crit_mr3_reduce_kernel", crit_mr3_reduce_kernel, dim3(1), dim3(kRedThreads), 0,
+                  as_stream(stream), P, W, out);
 }
 
 }  // namespace avr
@@ -665,13 +664,12 @@ extern "C" int avr_criterion_fwd2(int32_t B, int32_t F, const float* weights, co
     AVR_REQUIRE(B <= 256, "avr_criterion_fwd: at most 256 items per call");
     if (int e = launch_irfft(B, F, pred, ori, irtw, pred_time, ori_time, stream))
         return e;
-    hipLaunchKernelGGL(crit_stft_kernel, dim3(P.tiles_f, B), dim3(kThreads), 0, as_stream(stream),
-                       P, pred_time, ori_time, wtab, reinterpret_cast<const float2*>(tw512), W);
-    if (int e = check_launch("crit_stft_kernel")) return e;
-    hipLaunchKernelGGL(crit_reduce_kernel, dim3(1), dim3(kRedThreads), 0, as_stream(stream), P,
-                       reinterpret_cast<const float2*>(pred), reinterpret_cast<const float2*>(ori),
-                       pred_time, ori_time, W, losses, total);
-    return check_launch("crit_reduce_kernel");
+    if (int e = launch("crit_stft_kernel", crit_stft_kernel, dim3(P.tiles_f, B), dim3(kThreads), 0, as_stream(stream),
+                       P, pred_time, ori_time, wtab, reinterpret_cast<const float2*>(tw512), W))
+        return e;
+    return launch("crit_reduce_kernel", crit_reduce_kernel, dim3(1), dim3(kRedThreads), 0, as_stream(stream), P,
+                  reinterpret_cast<const float2*>(pred), reinterpret_cast<const float2*>(ori), pred_time, ori_time,
+                  W, losses, total);
 }
 
 extern "C" int avr_criterion_bwd(int32_t B, int32_t F, const float* weights, const float* pred,
@@ -686,22 +684,15 @@ extern "C" int avr_criterion_bwd(int32_t B, int32_t F, const float* weights, con
                 "avr_criterion_bwd: null pointer");
     CritWs W = carve(P, ws);
     AVR_REQUIRE(ws_bytes >= W.bytes, "avr_criterion_bwd: workspace too small");
-    hipLaunchKernelGGL(crit_bwd_frames_kernel, dim3(P.tiles_b, B), dim3(kThreads), 0,
-                       as_stream(stream), P, wtab, reinterpret_cast<const float2*>(tw512),
-                       grad_losses, W);
-    if (int e = check_launch("crit_bwd_frames_kernel")) return e;
-    hipLaunchKernelGGL(crit_bwd_time_kernel, dim3((P.n + kThreads - 1) / kThreads, B),
-                       dim3(kThreads), 0, as_stream(stream), P, pred_time, ori_time, grad_losses,
-                       grad_pred_time, W);
-    if (int e = check_launch("crit_bwd_time_kernel")) return e;
+    if (int e = launch("crit_bwd_frames_kernel", crit_bwd_frames_kernel, dim3(P.tiles_b, B), dim3(kThreads), 0,
+                       as_stream(stream), P, wtab, reinterpret_cast<const float2*>(tw512), grad_losses, W))
+        return e;
+    if (int e = launch("crit_bwd_time_kernel", crit_bwd_time_kernel, dim3((P.n + kThreads - 1) / kThreads, B),
+                       dim3(kThreads), 0, as_stream(stream), P, pred_time, ori_time, grad_losses, grad_pred_time, W))
+        return e;
+    // above 64 KiB from n >= 5462; make_plan's n <= 12288 keeps it (plus 2112 B static) inside 160 KiB
     const size_t lds = (size_t)P.n * 3 * sizeof(float);
-    if (lds > 65536)  // n >= 5462; make_plan's n <= 12288 keeps it (plus 2112 B static) inside 160 KiB
-        (void)hipFuncSetAttribute((const void*)crit_bwd_spec_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
-    hipLaunchKernelGGL(crit_bwd_spec_kernel, dim3((F + 31) / 32, B), dim3(kThreads), lds,
-                       as_stream(stream), P, reinterpret_cast<const float2*>(pred),
-                       reinterpret_cast<const float2*>(ori),
-                       reinterpret_cast<const float2*>(irtw), grad_losses, W,
-                       reinterpret_cast<float2*>(grad_pred));
-    return check_launch("crit_bwd_spec_kernel");
+    return launch("crit_bwd_spec_kernel", crit_bwd_spec_kernel, dim3((F + 31) / 32, B), dim3(kThreads), lds,
+                  as_stream(stream), P, reinterpret_cast<const float2*>(pred), reinterpret_cast<const float2*>(ori),
+                  reinterpret_cast<const float2*>(irtw), grad_losses, W, reinterpret_cast<float2*>(grad_pred));
 }

@@ -367,15 +367,14 @@ extern "C" int avr_das_fwd(int32_t n, const float* pred_time, const float* ori_t
                 "avr_das_fwd: bad args");
     DasWs W = carve(ws);
     AVR_REQUIRE(ws_bytes >= W.bytes, "avr_das_fwd: workspace too small");
-    hipLaunchKernelGGL(das_spectrum_kernel, dim3(kMics, 2), dim3(kThreads), 0, as_stream(stream),
-                       (int)n, pred_time, ori_time, reinterpret_cast<const float2*>(tw512), W);
-    if (int e = check_launch("das_spectrum_kernel")) return e;
-    hipLaunchKernelGGL(das_power_kernel, dim3(kFTiles, 2), dim3(kThreads), 0, as_stream(stream),
-                       reinterpret_cast<const float2*>(steer), W);
-    if (int e = check_launch("das_power_kernel")) return e;
-    hipLaunchKernelGGL(das_loss_kernel, dim3(1), dim3(512), 0, as_stream(stream), angles, beta,
-                       w_reg, w_ce, W, losses);
-    return check_launch("das_loss_kernel");
+    if (int e = launch("das_spectrum_kernel", das_spectrum_kernel, dim3(kMics, 2), dim3(kThreads), 0,
+                       as_stream(stream), (int)n, pred_time, ori_time, reinterpret_cast<const float2*>(tw512), W))
+        return e;
+    if (int e = launch("das_power_kernel", das_power_kernel, dim3(kFTiles, 2), dim3(kThreads), 0, as_stream(stream),
+                       reinterpret_cast<const float2*>(steer), W))
+        return e;
+    return launch("das_loss_kernel", das_loss_kernel, dim3(1), dim3(512), 0, as_stream(stream), angles, beta, w_reg,
+                  w_ce, W, losses);
 }
 
 extern "C" int avr_das_bwd(int32_t n, const float* steer, const float* angles,
@@ -386,11 +385,9 @@ extern "C" int avr_das_bwd(int32_t n, const float* steer, const float* angles,
                 "avr_das_bwd: bad args");
     DasWs W = carve(ws);
     AVR_REQUIRE(ws_bytes >= W.bytes, "avr_das_bwd: workspace too small");
-    hipLaunchKernelGGL(das_bwd_beam_kernel, dim3(kFTiles), dim3(512), 0, as_stream(stream),
-                       reinterpret_cast<const float2*>(steer), angles, beta, w_reg, w_ce,
-                       grad_losses, W);
-    if (int e = check_launch("das_bwd_beam_kernel")) return e;
-    hipLaunchKernelGGL(das_bwd_time_kernel, dim3(kMics), dim3(kThreads), 0, as_stream(stream),
-                       (int)n, reinterpret_cast<const float2*>(tw512), W, grad_pred_time);
-    return check_launch("das_bwd_time_kernel");
+    if (int e = launch("das_bwd_beam_kernel", das_bwd_beam_kernel, dim3(kFTiles), dim3(512), 0, as_stream(stream),
+                       reinterpret_cast<const float2*>(steer), angles, beta, w_reg, w_ce, grad_losses, W))
+        return e;
+    return launch("das_bwd_time_kernel", das_bwd_time_kernel, dim3(kMics), dim3(kThreads), 0, as_stream(stream),
+                  (int)n, reinterpret_cast<const float2*>(tw512), W, grad_pred_time);
 }

@@ -353,21 +353,26 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(int64_t N, int L, int
 }
 
 // points walked per 16-lane group
-inline int bwd_run() { return 16; }
+constexpr int kAtomicRun = 16;
 
-template <typename Tg>
-void launch_bwd(hipStream_t st, int64_t N, int L, const float* x, const Tg* gout, const LevelTable& lt,
-                float* gparams) {
-    const int run = bwd_run();
-    const int64_t pts_per_block = 16 * (int64_t)run;  // 16 groups of 16 lanes
+// the atomic backward, for a gradient of grad_dtype (fp32 or fp16)
+int launch_bwd(const char* what, hipStream_t st, int64_t N, int L, const float* x, const void* gout,
+               int32_t grad_dtype, const LevelTable& lt, float* gparams) {
+    const int64_t pts_per_block = 16 * (int64_t)kAtomicRun;  // 16 groups of 16 lanes
     const dim3 grid((unsigned)((N + pts_per_block - 1) / pts_per_block), (unsigned)L);
-#define AVR_HG_BWD(I)                                                                                          \
-    if (run == I) {                                                                                            \
-        hipLaunchKernelGGL((hashgrid_bwd_kernel<Tg, I>), grid, dim3(256), 0, st, N, L, 0, x, gout, lt, gparams); \
-        return;                                                                                                \
-    }
-    AVR_HG_BWD(1) AVR_HG_BWD(4) AVR_HG_BWD(8) AVR_HG_BWD(16) AVR_HG_BWD(32)
-#undef AVR_HG_BWD
+    return dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16>(grad_dtype, what, [&](auto tag) {
+        using Tg = typename decltype(tag)::type;
+        return launch(what, hashgrid_bwd_kernel<Tg, kAtomicRun>, grid, dim3(256), 0, st, N, L, 0, x, (const Tg*)gout,
+                      lt, gparams);
+    });
+}
+
+// the forward's (table, output) dtype pairs: fp32 or fp16 each
+template <typename F>
+int dispatch_fwd_dtypes(int32_t param_dtype, int32_t out_dtype, const char* what, F&& f) {
+    return dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16>(param_dtype, what, [&](auto pt) {
+        return dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16>(out_dtype, what, [&](auto ot) { return f(pt, ot); });
+    });
 }
 
 int make_table(int L, const int64_t* off, const float* scale, const int32_t* res, LevelTable* lt) {
@@ -381,20 +386,6 @@ int make_table(int L, const int64_t* off, const float* scale, const int32_t* res
     return 0;
 }
 
-template <typename Tp, typename To, bool ROW_MAJOR>
-void launch_lm(dim3 grid, hipStream_t st, int64_t N, const float* x, const void* params, LevelTable lt,
-               void* out, bool grp, int unit) {
-    if constexpr (std::is_same_v<Tp, __half>) {
-        if (grp) {
-            hipLaunchKernelGGL((hashgrid_fwd_lm_kernel<Tp, To, ROW_MAJOR, true>), grid, dim3(256), 0, st, N,
-                               x, (const Tp*)params, lt, (To*)out, unit);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((hashgrid_fwd_lm_kernel<Tp, To, ROW_MAJOR, false>), grid, dim3(256), 0, st, N, x,
-                           (const Tp*)params, lt, (To*)out, unit);
-}
-
 // Level-major forward launch; grouped corner loads for fp16 tables whose
 // base is 16-byte aligned (level offsets are multiples of 8 entries).  fp32
 // tables keep the 8-byte loads: a 16-byte group holds only 2 entries there
@@ -402,20 +393,17 @@ void launch_lm(dim3 grid, hipStream_t st, int64_t N, const float* x, const void*
 // 156 us row-major); fp16: 113-117 -> 103-106 us level-major, 138-140 ->
 // 116-118 us row-major (profiles/r02_hashgrid_group_ab.jsonl)
 template <bool ROW_MAJOR>
-int launch_fwd_lm(dim3 grid, hipStream_t st, int64_t N, const float* x, const void* params,
+int launch_fwd_lm(const char* what, dim3 grid, hipStream_t st, int64_t N, const float* x, const void* params,
                   int32_t param_dtype, const LevelTable& lt, void* out, int32_t out_dtype, int unit = 0) {
     const bool grp = group_loads() && ((uintptr_t)params & 15) == 0;
-    if (param_dtype == AVR_DTYPE_F32 && out_dtype == AVR_DTYPE_F32)
-        launch_lm<float, float, ROW_MAJOR>(grid, st, N, x, params, lt, out, grp, unit);
-    else if (param_dtype == AVR_DTYPE_F32 && out_dtype == AVR_DTYPE_F16)
-        launch_lm<float, __half, ROW_MAJOR>(grid, st, N, x, params, lt, out, grp, unit);
-    else if (param_dtype == AVR_DTYPE_F16 && out_dtype == AVR_DTYPE_F16)
-        launch_lm<__half, __half, ROW_MAJOR>(grid, st, N, x, params, lt, out, grp, unit);
-    else if (param_dtype == AVR_DTYPE_F16 && out_dtype == AVR_DTYPE_F32)
-        launch_lm<__half, float, ROW_MAJOR>(grid, st, N, x, params, lt, out, grp, unit);
-    else
-        return fail(AVR_E_ARG, "avr_hashgrid_fwd: unknown dtype");
-    return 0;
+    return dispatch_fwd_dtypes(param_dtype, out_dtype, what, [&](auto pt, auto ot) {
+        using Tp = typename decltype(pt)::type;
+        using To = typename decltype(ot)::type;
+        auto kern = hashgrid_fwd_lm_kernel<Tp, To, ROW_MAJOR, false>;
+        if constexpr (std::is_same_v<Tp, __half>)
+            if (grp) kern = hashgrid_fwd_lm_kernel<Tp, To, ROW_MAJOR, true>;
+        return launch(what, kern, grid, dim3(256), 0, st, N, x, (const Tp*)params, lt, (To*)out, unit);
+    });
 }
 
 // ------------------------------------------- partitioned backward (no atomics)
@@ -1020,24 +1008,14 @@ extern "C" int avr_hashgrid_fwd(int64_t N, int32_t n_levels, const float* x, con
     // time), same values and output layout (tools/probe_hashgrid.py)
     if (N >= lm_min_points()) {
         const dim3 glm((unsigned)((N + 255) / 256), (unsigned)L);
-        if (int e = launch_fwd_lm<true>(glm, st, N, x, params, param_dtype, lt, out, out_dtype)) return e;
-        return check_launch("avr_hashgrid_fwd");
+        return launch_fwd_lm<true>("avr_hashgrid_fwd", glm, st, N, x, params, param_dtype, lt, out, out_dtype);
     }
-    if (param_dtype == AVR_DTYPE_F32 && out_dtype == AVR_DTYPE_F32)
-        hipLaunchKernelGGL((hashgrid_fwd_kernel<float, float>), grid, dim3(256), 0, st, N, L, x,
-                           (const float*)params, lt, (float*)out);
-    else if (param_dtype == AVR_DTYPE_F32 && out_dtype == AVR_DTYPE_F16)
-        hipLaunchKernelGGL((hashgrid_fwd_kernel<float, __half>), grid, dim3(256), 0, st, N, L, x,
-                           (const float*)params, lt, (__half*)out);
-    else if (param_dtype == AVR_DTYPE_F16 && out_dtype == AVR_DTYPE_F16)
-        hipLaunchKernelGGL((hashgrid_fwd_kernel<__half, __half>), grid, dim3(256), 0, st, N, L, x,
-                           (const __half*)params, lt, (__half*)out);
-    else if (param_dtype == AVR_DTYPE_F16 && out_dtype == AVR_DTYPE_F32)
-        hipLaunchKernelGGL((hashgrid_fwd_kernel<__half, float>), grid, dim3(256), 0, st, N, L, x,
-                           (const __half*)params, lt, (float*)out);
-    else
-        return fail(AVR_E_ARG, "avr_hashgrid_fwd: unknown dtype");
-    return check_launch("avr_hashgrid_fwd");
+    return dispatch_fwd_dtypes(param_dtype, out_dtype, "avr_hashgrid_fwd", [&](auto pt, auto ot) {
+        using Tp = typename decltype(pt)::type;
+        using To = typename decltype(ot)::type;
+        return launch("avr_hashgrid_fwd", hashgrid_fwd_kernel<Tp, To>, grid, dim3(256), 0, st, N, L, x,
+                      (const Tp*)params, lt, (To*)out);
+    });
 }
 
 extern "C" int avr_hashgrid_bwd(int64_t N, int32_t n_levels, const float* x, const void* grad_out,
@@ -1049,14 +1027,8 @@ extern "C" int avr_hashgrid_bwd(int64_t N, int32_t n_levels, const float* x, con
     if (N == 0) return 0;
     LevelTable lt;
     if (int e = make_table(n_levels, level_offset, level_scale, level_res, &lt)) return e;
-    hipStream_t st = as_stream(stream);
-    if (grad_dtype == AVR_DTYPE_F32)
-        launch_bwd<float>(st, N, (int)n_levels, x, (const float*)grad_out, lt, grad_params);
-    else if (grad_dtype == AVR_DTYPE_F16)
-        launch_bwd<__half>(st, N, (int)n_levels, x, (const __half*)grad_out, lt, grad_params);
-    else
-        return fail(AVR_E_ARG, "avr_hashgrid_bwd: unknown grad dtype");
-    return check_launch("avr_hashgrid_bwd");
+    return launch_bwd("avr_hashgrid_bwd", as_stream(stream), N, (int)n_levels, x, grad_out, grad_dtype, lt,
+                      grad_params);
 }
 
 namespace {
@@ -1069,9 +1041,8 @@ int fwd_lm(int64_t N, int32_t n_levels, const float* x, const void* params, int3
     LevelTable lt;
     if (int e = make_table(n_levels, level_offset, level_scale, level_res, &lt)) return e;
     const dim3 grid((unsigned)((N + 255) / 256), (unsigned)n_levels);
-    hipStream_t st = as_stream(stream);
-    if (int e = launch_fwd_lm<false>(grid, st, N, x, params, param_dtype, lt, out, out_dtype, unit)) return e;
-    return check_launch("avr_hashgrid_fwd_lm");
+    return launch_fwd_lm<false>("avr_hashgrid_fwd_lm", grid, as_stream(stream), N, x, params, param_dtype, lt, out,
+                                out_dtype, unit);
 }
 }  // namespace
 
@@ -1287,33 +1258,17 @@ extern "C" int avr_ray_pose_bias(int32_t B, int32_t R, int32_t S, const float* v
     const dim3 grid((unsigned)((rays + kBiasRays - 1) / kBiasRays));
     const int f16 = enc_dtype == AVR_DTYPE_F16;
     hipStream_t st = as_stream(stream);
-    if (R % kBias2Rays == 0 && !AVR_BIAS_V1) {
-        const dim3 grid2((unsigned)(rays / kBias2Rays));
-        if (param_dtype == AVR_DTYPE_F16)
-            hipLaunchKernelGGL(ray_pose_bias2_kernel<__half>, grid2, dim3(kBias2Threads), 0, st, (int)B, (int)R,
-                               (int)S, view, tx, (const __half*)dir_params, dl, (int)dir_levels,
-                               (const __half*)tx_params, tl, (int)tx_levels, f16, mlp_f16, w_dir, w_tx, (int)n_out,
-                               bias);
-        else if (param_dtype == AVR_DTYPE_F32)
-            hipLaunchKernelGGL(ray_pose_bias2_kernel<float>, grid2, dim3(kBias2Threads), 0, st, (int)B, (int)R,
-                               (int)S, view, tx, (const float*)dir_params, dl, (int)dir_levels,
-                               (const float*)tx_params, tl, (int)tx_levels, f16, mlp_f16, w_dir, w_tx, (int)n_out,
-                               bias);
-        else
-            return fail(AVR_E_ARG, "avr_ray_pose_bias: unknown param dtype");
-        return check_launch("avr_ray_pose_bias");
-    }
-    if (param_dtype == AVR_DTYPE_F16)
-        hipLaunchKernelGGL(ray_pose_bias_kernel<__half>, grid, dim3(256), 0, st, (int)B, (int)R, (int)S, view, tx,
-                           (const __half*)dir_params, dl, (int)dir_levels, (const __half*)tx_params, tl,
-                           (int)tx_levels, f16, mlp_f16, w_dir, w_tx, (int)n_out, bias);
-    else if (param_dtype == AVR_DTYPE_F32)
-        hipLaunchKernelGGL(ray_pose_bias_kernel<float>, grid, dim3(256), 0, st, (int)B, (int)R, (int)S, view, tx,
-                           (const float*)dir_params, dl, (int)dir_levels, (const float*)tx_params, tl,
-                           (int)tx_levels, f16, mlp_f16, w_dir, w_tx, (int)n_out, bias);
-    else
-        return fail(AVR_E_ARG, "avr_ray_pose_bias: unknown param dtype");
-    return check_launch("avr_ray_pose_bias");
+    const bool v2 = R % kBias2Rays == 0 && !AVR_BIAS_V1;
+    return dispatch_dtype<AVR_DTYPE_F16, AVR_DTYPE_F32>(param_dtype, "avr_ray_pose_bias", [&](auto tag) {
+        using Tp = typename decltype(tag)::type;
+        auto go = [&](auto kern, dim3 g, dim3 block) {
+            return launch("avr_ray_pose_bias", kern, g, block, 0, st, (int)B, (int)R, (int)S, view, tx,
+                          (const Tp*)dir_params, dl, (int)dir_levels, (const Tp*)tx_params, tl, (int)tx_levels, f16,
+                          mlp_f16, w_dir, w_tx, (int)n_out, bias);
+        };
+        if (v2) return go(ray_pose_bias2_kernel<Tp>, dim3((unsigned)(rays / kBias2Rays)), dim3(kBias2Threads));
+        return go(ray_pose_bias_kernel<Tp>, grid, dim3(256));
+    });
 }
 
 // Below this many points the atomic kernel is cheaper than the five
@@ -1349,6 +1304,7 @@ int bwd_partitioned(int64_t N, int32_t n_levels, const float* x, const void* gra
     if (int e = make_table(n_levels, level_offset, level_scale, level_res, &lt)) return e;
     hipStream_t st = as_stream(stream);
     const int L = n_levels;
+    const char* what = "avr_hashgrid_bwd_partitioned";
     // the overwrite form's atomic paths (few points, shapes the partitioned
     // passes do not take) add into a cleared gradient
     auto clear = [&]() -> bool {
@@ -1358,21 +1314,13 @@ int bwd_partitioned(int64_t N, int32_t n_levels, const float* x, const void* gra
     if (N == 0) return clear() ? 0 : fail(AVR_E_ARG, "avr_hashgrid_bwd_partitioned_set: clear failed");
     if (N < kPartitionedMinPoints) {  // few points: the atomic kernel (same += result)
         if (!clear()) return fail(AVR_E_ARG, "avr_hashgrid_bwd_partitioned_set: clear failed");
-        if (grad_dtype == AVR_DTYPE_F32)
-            launch_bwd<float>(st, N, L, x, (const float*)grad_out, lt, grad_params);
-        else
-            launch_bwd<__half>(st, N, L, x, (const __half*)grad_out, lt, grad_params);
-        return check_launch("avr_hashgrid_bwd_partitioned");
+        return launch_bwd(what, st, N, L, x, grad_out, grad_dtype, lt, grad_params);
     }
     BwdLayout b;
     if (bwd_layout(N, n_levels, level_offset, level_res, &b) != 0 || !b.scatter_ok) {
         // shapes the partitioned passes do not take: the atomic kernel (same += result)
         if (!clear()) return fail(AVR_E_ARG, "avr_hashgrid_bwd_partitioned_set: clear failed");
-        if (grad_dtype == AVR_DTYPE_F32)
-            launch_bwd<float>(st, N, L, x, (const float*)grad_out, lt, grad_params);
-        else
-            launch_bwd<__half>(st, N, L, x, (const __half*)grad_out, lt, grad_params);
-        return check_launch("avr_hashgrid_bwd_partitioned");
+        return launch_bwd(what, st, N, L, x, grad_out, grad_dtype, lt, grad_params);
     }
     AVR_REQUIRE(workspace_bytes >= b.bytes, "avr_hashgrid_bwd_partitioned: workspace too small");
     char* ws = static_cast<char*>(workspace);
@@ -1385,38 +1333,35 @@ int bwd_partitioned(int64_t N, int32_t n_levels, const float* x, const void* gra
     // every pass below reads the gradient level-major
     const dim3 tgrid((unsigned)((N + 63) / 64));
     void* glm = ws + b.glm;
-    if (grad_dtype == AVR_DTYPE_F32)
-        hipLaunchKernelGGL(hg_level_major_kernel<float>, tgrid, dim3(256), 64 * 2 * L * 4, st, N, L,
-                           (const float*)grad_out, (float*)glm);
-    else
-        hipLaunchKernelGGL(hg_level_major_kernel<__half>, tgrid, dim3(256), 64 * 2 * L * 2, st, N, L,
-                           (const __half*)grad_out, (__half*)glm);
-    grad_out = glm;
-    if (grad_dtype == AVR_DTYPE_F32)
-        hipLaunchKernelGGL(hg_bwd_count_kernel<float>, grid, dim3(256), lds_count, st, N, L, x,
-                           (const float*)grad_out, lt, b.plan, counts);
-    else
-        hipLaunchKernelGGL(hg_bwd_count_kernel<__half>, grid, dim3(256), lds_count, st, N, L, x,
-                           (const __half*)grad_out, lt, b.plan, counts);
     int* part_start = reinterpret_cast<int*>(ws + b.part_start);
     int* slice_base = reinterpret_cast<int*>(ws + b.slice_base);
-    hipLaunchKernelGGL(hg_bwd_scan_kernel, dim3((unsigned)((b.total_parts + 15) / 16)), dim3(1024), 0, st,
-                       b.total_parts, b.plan.nchunks, counts, totals);
-    hipLaunchKernelGGL(hg_bwd_plan_kernel, dim3(1), dim3(1024), 0, st, b.total_parts, b.plan, totals, part_start,
-                       slice_base);
-    if (grad_dtype == AVR_DTYPE_F32)
-        hipLaunchKernelGGL(hg_bwd_scatter_kernel<float>, grid, dim3(256), lds_scat, st, N, L, x,
-                           (const float*)grad_out, lt, b.plan, counts, totals, part_start, contrib);
-    else
-        hipLaunchKernelGGL(hg_bwd_scatter_kernel<__half>, grid, dim3(256), lds_scat, st, N, L, x,
-                           (const __half*)grad_out, lt, b.plan, counts, totals, part_start, contrib);
+    // level-major gradient, count, scan, plan, scatter: each stops the sequence if refused
+    if (int e = dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16>(grad_dtype, what, [&](auto tag) {
+            using Tg = typename decltype(tag)::type;
+            const Tg* g = (const Tg*)glm;
+            if (int e = launch(what, hg_level_major_kernel<Tg>, tgrid, dim3(256), 64 * 2 * L * sizeof(Tg), st, N, L,
+                               (const Tg*)grad_out, (Tg*)glm))
+                return e;
+            if (int e = launch(what, hg_bwd_count_kernel<Tg>, grid, dim3(256), lds_count, st, N, L, x, g, lt, b.plan,
+                               counts))
+                return e;
+            if (int e = launch(what, hg_bwd_scan_kernel, dim3((unsigned)((b.total_parts + 15) / 16)), dim3(1024), 0,
+                               st, b.total_parts, b.plan.nchunks, counts, totals))
+                return e;
+            if (int e = launch(what, hg_bwd_plan_kernel, dim3(1), dim3(1024), 0, st, b.total_parts, b.plan, totals,
+                               part_start, slice_base))
+                return e;
+            return launch(what, hg_bwd_scatter_kernel<Tg>, grid, dim3(256), lds_scat, st, N, L, x, g, lt, b.plan,
+                          counts, totals, part_start, contrib);
+        }))
+        return e;
     if (overwrite)
-        hipLaunchKernelGGL(hg_bwd_zero_hot_kernel, dim3((unsigned)b.total_parts), dim3(256), 0, st, lt, b.plan,
-                           b.total_parts, slice_base, grad_params);
-    hipLaunchKernelGGL(hg_bwd_reduce_kernel, dim3((unsigned)((b.max_slices + kReduceWaves - 1) / kReduceWaves)),
-                       dim3(64 * kReduceWaves), 0, st, lt, b.plan, b.total_parts, totals, part_start, slice_base,
-                       contrib, grad_params, (int)overwrite);
-    return check_launch("avr_hashgrid_bwd_partitioned");
+        if (int e = launch(what, hg_bwd_zero_hot_kernel, dim3((unsigned)b.total_parts), dim3(256), 0, st, lt, b.plan,
+                           b.total_parts, slice_base, grad_params))
+            return e;
+    return launch(what, hg_bwd_reduce_kernel, dim3((unsigned)((b.max_slices + kReduceWaves - 1) / kReduceWaves)),
+                  dim3(64 * kReduceWaves), 0, st, lt, b.plan, b.total_parts, totals, part_start, slice_base, contrib,
+                  grad_params, (int)overwrite);
 }
 }  // namespace
 

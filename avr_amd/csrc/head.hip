@@ -1082,12 +1082,6 @@ int head_shape(const avr_render_params& p, int B, int R, int K, int es, HeadShap
     return 0;
 }
 
-template <typename Kern>
-void allow_lds(Kern k, size_t lds) {
-    if (lds > 65536)
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
-
 int elem_size(int dtype) { return dtype == AVR_DTYPE_F32 ? 4 : 2; }
 
 int head_check(const avr_render_params* p, int B, int K, const void* h, const void* W, int dtype) {
@@ -1127,6 +1121,17 @@ void fwd_block(const HeadShape& hs, int dtype, int* kb, int* sb) {
     *sb = s;
 }
 
+// W [T][K] -> [K/kb][T][kb] of the head's dtype (head_check admits all three)
+int pack_w(const char* what, int T, int K, int kb, const void* W, int dtype, void* Wp, hipStream_t st) {
+    const int64_t n = (int64_t)T * K;
+    const int blocks = (int)std::min<int64_t>((n + kThreads - 1) / kThreads, 4096);
+    return dispatch_dtype<AVR_DTYPE_BF16, AVR_DTYPE_F16, AVR_DTYPE_F32>(dtype, what, [&](auto tag) {
+        using TH = typename decltype(tag)::type;
+        return launch(what, head_pack_w_kernel<TH>, dim3(blocks), dim3(kThreads), 0, st, T, K, kb, (const TH*)W,
+                      (TH*)Wp);
+    });
+}
+
 }  // namespace
 
 extern "C" int avr_head_pack_w(const avr_render_params* p, int32_t B, int32_t K, const void* W, int32_t dtype,
@@ -1137,20 +1142,7 @@ extern "C" int avr_head_pack_w(const avr_render_params* p, int32_t B, int32_t K,
     if (int e = head_shape(*p, B, n_rays(*p), K, elem_size(dtype), &hs)) return e;
     int kbf, sb;
     fwd_block(hs, dtype, &kbf, &sb);
-    const int T = p->T;
-    const int64_t n = (int64_t)T * K;
-    const int blocks = (int)std::min<int64_t>((n + kThreads - 1) / kThreads, 4096);
-    hipStream_t st = as_stream(stream);
-    if (dtype == AVR_DTYPE_BF16)
-        hipLaunchKernelGGL(head_pack_w_kernel<__hip_bfloat16>, dim3(blocks), dim3(kThreads), 0, st, T, (int)K, kbf,
-                           (const __hip_bfloat16*)W, (__hip_bfloat16*)Wp);
-    else if (dtype == AVR_DTYPE_F16)
-        hipLaunchKernelGGL(head_pack_w_kernel<__half>, dim3(blocks), dim3(kThreads), 0, st, T, (int)K, kbf,
-                           (const __half*)W, (__half*)Wp);
-    else
-        hipLaunchKernelGGL(head_pack_w_kernel<float>, dim3(blocks), dim3(kThreads), 0, st, T, (int)K, kbf,
-                           (const float*)W, (float*)Wp);
-    return check_launch("avr_head_pack_w");
+    return pack_w("avr_head_pack_w", p->T, K, kbf, W, dtype, Wp, as_stream(stream));
 }
 
 extern "C" int avr_head_splits(const avr_render_params* p, int32_t B, int32_t K, int32_t dtype,
@@ -1170,17 +1162,8 @@ extern "C" int avr_head_sort(const avr_render_params* p, int32_t B, const float*
     if (int e = head_shape(*p, B, R, 16, 4, &hs)) return e;
     hipStream_t st = as_stream(stream);
     const dim3 grid(p->n_samples, B);
-    auto go = [&](auto kern) {
-        allow_lds(kern, hs.lds_sort);
-        hipLaunchKernelGGL(kern, grid, dim3(kThreads), hs.lds_sort, st, *p, R, w, delay, perm, ws, cnt);
-    };
-    if (hs.rpt == 4)
-        go(head_sort_kernel<4>);
-    else if (hs.rpt == 8)
-        go(head_sort_kernel<8>);
-    else
-        go(head_sort_kernel<16>);
-    return check_launch("avr_head_sort");
+    auto kern = hs.rpt == 4 ? head_sort_kernel<4> : hs.rpt == 8 ? head_sort_kernel<8> : head_sort_kernel<16>;
+    return launch("avr_head_sort", kern, grid, dim3(kThreads), hs.lds_sort, st, *p, R, w, delay, perm, ws, cnt);
 }
 
 extern "C" int avr_head_fwd(const avr_render_params* p, int32_t B, int32_t K, const void* h,
@@ -1199,36 +1182,25 @@ extern "C" int avr_head_fwd(const avr_render_params* p, int32_t B, int32_t K, co
     HeadShape hf = hs;
     hf.kb = kbf;
     hf.lds_c = cumsum_lds_bytes(R, kbf);
-    auto go = [&](auto kern, auto hp, auto wp) {
-        allow_lds(kern, hf.lds_c);
-        hipLaunchKernelGGL(kern, grid, dim3(kThreads), hf.lds_c, st, *p, (int)B, R, (int)K, hf.kg, hp, wp,
-                           perm, ws, cnt, zpart);
-    };
-#define AVR_HF(TH, KBV, NTV, RP)                                                                   \
+#define AVR_HF(KBV, NTV, RP)                                                                       \
     if (hf.kb == KBV && hf.nt == NTV && hf.rpt == RP) {                                            \
         constexpr bool kSb = sizeof(TH) == 2 && RP <= 8;                                            \
-        if (kSb && sb == 2)                                                                         \
-            go(head_fwd_kernel<TH, KBV, NTV, RP, kSb ? 2 : 1>, (const TH*)h, (const TH*)W);         \
-        else if (kSb && sb == 4)                                                                    \
-            go(head_fwd_kernel<TH, KBV, NTV, RP, kSb ? 4 : 1>, (const TH*)h, (const TH*)W);         \
-        else                                                                                        \
-            go(head_fwd_kernel<TH, KBV, NTV, RP, 1>, (const TH*)h, (const TH*)W);                   \
+        if (kSb && sb == 2) return go(head_fwd_kernel<TH, KBV, NTV, RP, kSb ? 2 : 1>);              \
+        if (kSb && sb == 4) return go(head_fwd_kernel<TH, KBV, NTV, RP, kSb ? 4 : 1>);              \
+        return go(head_fwd_kernel<TH, KBV, NTV, RP, 1>);                                            \
     }
-#define AVR_HF_R(TH, KBV, NTV) AVR_HF(TH, KBV, NTV, 4) AVR_HF(TH, KBV, NTV, 8) AVR_HF(TH, KBV, NTV, 16)
-#define AVR_HF_ALL(TH)                                                                             \
-    AVR_HF_R(TH, 4, 4) AVR_HF_R(TH, 4, 8) AVR_HF_R(TH, 4, 16) AVR_HF_R(TH, 8, 4) AVR_HF_R(TH, 8, 8) \
-    AVR_HF_R(TH, 16, 4)
-    if (dtype == AVR_DTYPE_BF16) {
-        AVR_HF_ALL(__hip_bfloat16)
-    } else if (dtype == AVR_DTYPE_F16) {
-        AVR_HF_ALL(__half)
-    } else {
-        AVR_HF_ALL(float)
-    }
+#define AVR_HF_R(KBV, NTV) AVR_HF(KBV, NTV, 4) AVR_HF(KBV, NTV, 8) AVR_HF(KBV, NTV, 16)
+    return dispatch_dtype<AVR_DTYPE_BF16, AVR_DTYPE_F16, AVR_DTYPE_F32>(dtype, "avr_head_fwd", [&](auto tag) {
+        using TH = typename decltype(tag)::type;
+        auto go = [&](auto kern) {
+            return launch("avr_head_fwd", kern, grid, dim3(kThreads), hf.lds_c, st, *p, (int)B, R, (int)K, hf.kg,
+                          (const TH*)h, (const TH*)W, perm, ws, cnt, zpart);
+        };
+        AVR_HF_R(4, 4) AVR_HF_R(4, 8) AVR_HF_R(4, 16) AVR_HF_R(8, 4) AVR_HF_R(8, 8) AVR_HF_R(16, 4)
+        return fail(AVR_E_CONFIG, "avr_head_fwd: no kernel for this block shape");
+    });
 #undef AVR_HF_R
-#undef AVR_HF_ALL
 #undef AVR_HF
-    return check_launch("avr_head_fwd");
 }
 
 // the block-sum form of dL/dh (head_bwd_h_blk) serves K % 8 == 0; its dL/dw
@@ -1300,84 +1272,57 @@ extern "C" int avr_head_bwd2(const avr_render_params* p, int32_t B, int32_t K, c
     float* Ssum = Lsum + (int64_t)B * S * hb_nblk(T) * K;
     float* Csum = Ssum + (int64_t)B * S * hb_nseg(T) * K;
     hipStream_t st = as_stream(stream);
-    if (!blk) {  // (the scan form's packed W)
-        const int64_t n = (int64_t)T * K;
-        const int blocks = (int)std::min<int64_t>((n + kThreads - 1) / kThreads, 4096);
-        if (dtype == AVR_DTYPE_BF16)
-            hipLaunchKernelGGL(head_pack_w_kernel<__hip_bfloat16>, dim3(blocks), dim3(kThreads), 0, st, T,
-                               (int)K, hs.kb, (const __hip_bfloat16*)W, (__hip_bfloat16*)Wb);
-        else if (dtype == AVR_DTYPE_F16)
-            hipLaunchKernelGGL(head_pack_w_kernel<__half>, dim3(blocks), dim3(kThreads), 0, st, T,
-                               (int)K, hs.kb, (const __half*)W, (__half*)Wb);
-        else
-            hipLaunchKernelGGL(head_pack_w_kernel<float>, dim3(blocks), dim3(kThreads), 0, st, T, (int)K, hs.kb,
-                               (const float*)W, (float*)Wb);
-    }
+    const char* what = "avr_head_bwd";
+    if (!blk)  // (the scan form's packed W)
+        if (int e = pack_w(what, T, K, hs.kb, W, dtype, Wb, st)) return e;
     // 16-bit h: h loads / grad_h stores 2 feature blocks (32 B) per row
     const int bsb = (elem_size(dtype) == 2 && hs.kg % (2 * hs.kb) == 0) ? 2 : 1;
-    auto go_h = [&](auto kern, auto hp, auto wp, auto gp) {
-        if (blk) return;  // (the block-sum form below)
-        allow_lds(kern, hs.lds_q);
-        hipLaunchKernelGGL(kern, dim3(hs.n_kg, S, B), dim3(kThreads), hs.lds_q, st, *p, (int)B, R, (int)K,
-                           hs.kg, hp, wp, w, delay, gz, gp, gw_part, (int)relu_mask);
-    };
-    auto go_w = [&](auto kern, auto hp) {
-        allow_lds(kern, hs.lds_c);
-        hipLaunchKernelGGL(kern, dim3(K / hs.kb, n_sg, B), dim3(kThreads), hs.lds_c, st, *p, (int)B, R,
-                           (int)K, s_per, hp, perm, ws, cnt, gz, gW_part);
-    };
-#define AVR_HB(TH, KBV, NTV, RP)                                                                   \
+    // dL/dh in the scan form (the block shape's kernel `kh`) or the block-sum
+    // form, and dL/dW (`kw`), each stopping the sequence if refused
+#define AVR_HB(KBV, NTV, RP)                                                                       \
     if (hs.kb == KBV && hs.nt == NTV && hs.rpt == RP) {                                            \
-        if constexpr (sizeof(TH) == 2 && RP <= 8) {                                                \
-            if (bsb == 2)                                                                           \
-                go_h(head_bwd_h_kernel<TH, KBV, NTV, RP, 2>, (const TH*)h, (const TH*)Wb, (TH*)grad_h); \
-            else                                                                                    \
-                go_h(head_bwd_h_kernel<TH, KBV, NTV, RP, 1>, (const TH*)h, (const TH*)Wb, (TH*)grad_h); \
-        } else {                                                                                    \
-            go_h(head_bwd_h_kernel<TH, KBV, NTV, RP, 1>, (const TH*)h, (const TH*)Wb, (TH*)grad_h);   \
-        }                                                                                           \
-        go_w(head_bwd_w_kernel<TH, KBV, NTV, RP>, (const TH*)h);                                   \
+        auto kh = head_bwd_h_kernel<TH, KBV, NTV, RP, 1>;                                           \
+        if constexpr (sizeof(TH) == 2 && RP <= 8)                                                  \
+            if (bsb == 2) kh = head_bwd_h_kernel<TH, KBV, NTV, RP, 2>;                              \
+        return go(kh, head_bwd_w_kernel<TH, KBV, NTV, RP>);                                         \
     }
-#define AVR_HB_R(TH, KBV, NTV) AVR_HB(TH, KBV, NTV, 4) AVR_HB(TH, KBV, NTV, 8) AVR_HB(TH, KBV, NTV, 16)
-#define AVR_HB_ALL(TH)                                                                             \
-    AVR_HB_R(TH, 4, 4) AVR_HB_R(TH, 4, 8) AVR_HB_R(TH, 4, 16) AVR_HB_R(TH, 8, 4) AVR_HB_R(TH, 8, 8) \
-    AVR_HB_R(TH, 16, 4)
-    if (dtype == AVR_DTYPE_BF16) {
-        AVR_HB_ALL(__hip_bfloat16)
-    } else if (dtype == AVR_DTYPE_F16) {
-        AVR_HB_ALL(__half)
-    } else {
-        AVR_HB_ALL(float)
-    }
+#define AVR_HB_R(KBV, NTV) AVR_HB(KBV, NTV, 4) AVR_HB(KBV, NTV, 8) AVR_HB(KBV, NTV, 16)
+    if (int e = dispatch_dtype<AVR_DTYPE_BF16, AVR_DTYPE_F16, AVR_DTYPE_F32>(dtype, what, [&](auto tag) {
+            using TH = typename decltype(tag)::type;
+            auto go = [&](auto kh, auto kw) {
+                if (!blk)
+                    if (int e = launch(what, kh, dim3(hs.n_kg, S, B), dim3(kThreads), hs.lds_q, st, *p, (int)B, R,
+                                       (int)K, hs.kg, (const TH*)h, (const TH*)Wb, w, delay, gz, (TH*)grad_h,
+                                       gw_part, (int)relu_mask))
+                        return e;
+                if (int e = launch(what, kw, dim3(K / hs.kb, n_sg, B), dim3(kThreads), hs.lds_c, st, *p, (int)B, R,
+                                   (int)K, s_per, (const TH*)h, perm, ws, cnt, gz, gW_part))
+                    return e;
+                if (!blk) return 0;
+                const unsigned nfg = (unsigned)((K + kHbFeat - 1) / kHbFeat);
+                const dim3 gs(nfg, (unsigned)hb_nseg(T), (unsigned)(B * S));
+                const dim3 gh(nfg, (unsigned)((R + 15) / 16), (unsigned)(B * S));
+                const int64_t nck = (int64_t)B * S * K;
+                if (int e = launch(what, head_bwd_suffix_kernel<TH>, gs, dim3(64), 0, st, *p, (int)K, (const TH*)W,
+                                   gz, Lsum, Ssum))
+                    return e;
+                if (int e = launch(what, head_bwd_carry_kernel, dim3((unsigned)((nck + 255) / 256)), dim3(256), 0,
+                                   st, T, (int)K, nck, Ssum, Csum))
+                    return e;
+                return launch(what, head_bwd_h_blk_kernel<TH>, gh, dim3(256), 0, st, *p, (int)B, R, (int)K,
+                              (const TH*)h, (const TH*)W, w, delay, gz, Lsum, Csum, (TH*)grad_h, gw_part,
+                              (int)relu_mask);
+            };
+            AVR_HB_R(4, 4) AVR_HB_R(4, 8) AVR_HB_R(4, 16) AVR_HB_R(8, 4) AVR_HB_R(8, 8) AVR_HB_R(16, 4)
+            return fail(AVR_E_CONFIG, "avr_head_bwd: no kernel for this block shape");
+        }))
+        return e;
 #undef AVR_HB_R
-#undef AVR_HB_ALL
 #undef AVR_HB
-    if (int e = check_launch("avr_head_bwd")) return e;
-    if (blk) {
-        const unsigned nfg = (unsigned)((K + kHbFeat - 1) / kHbFeat);
-        const dim3 gs(nfg, (unsigned)hb_nseg(T), (unsigned)(B * S));
-        const dim3 gh(nfg, (unsigned)((R + 15) / 16), (unsigned)(B * S));
-        const int64_t nck = (int64_t)B * S * K;
-#define AVR_HBLK(TH)                                                                                        \
-    hipLaunchKernelGGL(head_bwd_suffix_kernel<TH>, gs, dim3(64), 0, st, *p, (int)K, (const TH*)W, gz, Lsum, Ssum); \
-    hipLaunchKernelGGL(head_bwd_carry_kernel, dim3((unsigned)((nck + 255) / 256)), dim3(256), 0, st, T, (int)K,   \
-                       nck, Ssum, Csum);                                                                     \
-    hipLaunchKernelGGL(head_bwd_h_blk_kernel<TH>, gh, dim3(256), 0, st, *p, (int)B, R, (int)K, (const TH*)h,     \
-                       (const TH*)W, w, delay, gz, Lsum, Csum, (TH*)grad_h, gw_part, (int)relu_mask);
-        if (dtype == AVR_DTYPE_BF16) {
-            AVR_HBLK(__hip_bfloat16)
-        } else if (dtype == AVR_DTYPE_F16) {
-            AVR_HBLK(__half)
-        } else {
-            AVR_HBLK(float)
-        }
-#undef AVR_HBLK
-        if (int e = check_launch("avr_head_bwd")) return e;
-    }
     const int64_t n1 = (int64_t)B * R * S, n2 = (int64_t)T * K;
-    hipLaunchKernelGGL(sum_parts_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, st, n1,
-                       n_parts, gw_part, grad_w);
-    hipLaunchKernelGGL(sum_parts_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, n2,
-                       (int)(B * n_sg), gW_part, grad_W);
-    return check_launch("avr_head_bwd_sum");
+    if (int e = launch("avr_head_bwd_sum", sum_parts_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, st,
+                       n1, n_parts, gw_part, grad_w))
+        return e;
+    return launch("avr_head_bwd_sum", sum_parts_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, n2,
+                  (int)(B * n_sg), gW_part, grad_W);
 }

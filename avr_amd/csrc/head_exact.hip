@@ -589,12 +589,6 @@ int exact_splits(int R, int T, int K) {
     return n;
 }
 
-template <typename Kern>
-void allow_lds(Kern k, size_t lds) {
-    if (lds > 65536)
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
-
 }  // namespace
 
 extern "C" int avr_head_exact_layout(const avr_render_params* p, int32_t B, int32_t K, int32_t dtype,
@@ -618,9 +612,8 @@ extern "C" int avr_head_pack_w_exact(const avr_render_params* p, int32_t K, cons
     const int T = p->T, KSM = exact_ksm(K);
     const int64_t n = (int64_t)((T + 63) / 64) * 2 * KSM * 64;
     const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(head_pack_exact_kernel<__half>, dim3(blocks), dim3(256), 0, as_stream(stream), T, (int)K,
-                       KSM, (const uint16_t*)W, (frag8*)Wf, n);
-    return check_launch("avr_head_pack_w_exact");
+    return launch("avr_head_pack_w_exact", head_pack_exact_kernel<__half>, dim3(blocks), dim3(256), 0,
+                  as_stream(stream), T, (int)K, KSM, (const uint16_t*)W, (frag8*)Wf, n);
 }
 
 extern "C" int avr_head_fwd_exact(const avr_render_params* p, int32_t B, int32_t K, const void* h, const void* Wf,
@@ -647,11 +640,10 @@ extern "C" int avr_head_fwd_exact(const avr_render_params* p, int32_t B, int32_t
     // the 4-wave items (two workgroups per CU) lose with it (252 vs 244)
     int prio = small ? 0 : 1;
     if (const char* pe = AVR_PROBE_ENV("AVR_EXACT_PRIO_PROBE")) prio = atoi(pe);
-    auto run = [&](auto e_tag) {
-        using E = decltype(e_tag);
+    return dispatch_dtype<AVR_DTYPE_F16, AVR_DTYPE_BF16>(dtype, "avr_head_fwd_exact", [&](auto e_tag) {
+        using E = typename decltype(e_tag)::type;
         auto go = [&](auto kern, int ksm, int waves, int rays, int nb, int nc, const void* hv) {
             const size_t lds = xs_lds_bytes(ksm, T, waves, rays, nb, nc);
-            allow_lds(kern, lds);
             // persistent workgroups: as many as fit on the chip at once (a
             // multiple of 8: one work queue per XCD), at most one per 8 items
             int per_cu = 1;
@@ -661,27 +653,20 @@ extern "C" int avr_head_fwd_exact(const avr_render_params* p, int32_t B, int32_t
             const int64_t gq = std::min<int64_t>((int64_t)device_cus() * per_cu / 8, (items + 7) / 8);
             const int grid = 8 * (int)std::max<int64_t>(gq, 1);
             (void)hipMemsetAsync(queue, 0, kExactQueueInts * sizeof(int32_t), st);
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * waves), lds, st, *p, (int)B, R, (int)K, (const E*)hv,
-                               (const frag8*)Wf, perm, ws, cnt, delay, zpart, (int*)queue, (int)items, prio);
+            return launch("avr_head_fwd_exact", kern, dim3(grid), dim3(64 * waves), lds, st, *p, (int)B, R, (int)K,
+                          (const E*)hv, (const frag8*)Wf, perm, ws, cnt, delay, zpart, (int*)queue, (int)items, prio);
         };
         const bool rowdma = K == 512;
         if (small) {
-            if (KSM == 8) go(head_exact_kernel<E, 8, 4, 128, 2, 1, false>, 8, 4, 128, 2, 1, h);
-            else if (KSM == 16) go(head_exact_kernel<E, 16, 4, 128, 2, 1, false>, 16, 4, 128, 2, 1, h);
-            else if (rowdma) go(head_exact_kernel<E, 32, 4, 128, 2, 1, true>, 32, 4, 128, 2, 1, h);
-            else go(head_exact_kernel<E, 32, 4, 128, 2, 1, false>, 32, 4, 128, 2, 1, h);
-        } else if (tt64 && rowdma) {
-            go(head_exact_kernel<E, 32, 8, 256, 2, 2, true>, 32, 8, 256, 2, 2, h);
-        } else {
-            if (KSM == 8) go(head_exact_kernel<E, 8, 8, 256, 4, 1, false>, 8, 8, 256, 4, 1, h);
-            else if (KSM == 16) go(head_exact_kernel<E, 16, 8, 256, 4, 1, false>, 16, 8, 256, 4, 1, h);
-            else if (rowdma) go(head_exact_kernel<E, 32, 8, 256, 4, 1, true>, 32, 8, 256, 4, 1, h);
-            else go(head_exact_kernel<E, 32, 8, 256, 4, 1, false>, 32, 8, 256, 4, 1, h);
+            if (KSM == 8) return go(head_exact_kernel<E, 8, 4, 128, 2, 1, false>, 8, 4, 128, 2, 1, h);
+            if (KSM == 16) return go(head_exact_kernel<E, 16, 4, 128, 2, 1, false>, 16, 4, 128, 2, 1, h);
+            if (rowdma) return go(head_exact_kernel<E, 32, 4, 128, 2, 1, true>, 32, 4, 128, 2, 1, h);
+            return go(head_exact_kernel<E, 32, 4, 128, 2, 1, false>, 32, 4, 128, 2, 1, h);
         }
-    };
-    if (dtype == AVR_DTYPE_F16)
-        run(__half{});
-    else
-        run(__hip_bfloat16{});
-    return check_launch("avr_head_fwd_exact");
+        if (tt64 && rowdma) return go(head_exact_kernel<E, 32, 8, 256, 2, 2, true>, 32, 8, 256, 2, 2, h);
+        if (KSM == 8) return go(head_exact_kernel<E, 8, 8, 256, 4, 1, false>, 8, 8, 256, 4, 1, h);
+        if (KSM == 16) return go(head_exact_kernel<E, 16, 8, 256, 4, 1, false>, 16, 8, 256, 4, 1, h);
+        if (rowdma) return go(head_exact_kernel<E, 32, 8, 256, 4, 1, true>, 32, 8, 256, 4, 1, h);
+        return go(head_exact_kernel<E, 32, 8, 256, 4, 1, false>, 32, 8, 256, 4, 1, h);
+    });
 }

@@ -333,9 +333,8 @@ extern "C" int avr_linear512_pack_w2(const void* W, int32_t dtype, int32_t trans
     AVR_REQUIRE(reinterpret_cast<uintptr_t>(W) % 16 == 0 && reinterpret_cast<uintptr_t>(Wf) % 16 == 0,
                 "avr_linear512_pack_w: W and Wf must be 16-byte aligned");
     const int64_t n = (int64_t)kLK * kLK / 8;  // 16-byte fragments rows
-    hipLaunchKernelGGL(linear512_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream),
-                       (const uint16_t*)W, (frag8*)Wf, n, (int)transpose);
-    return check_launch("avr_linear512_pack_w");
+    return launch("avr_linear512_pack_w", linear512_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                  as_stream(stream), (const uint16_t*)W, (frag8*)Wf, n, (int)transpose);
 }
 
 namespace {
@@ -355,28 +354,18 @@ int linear512_launch(int64_t M, const void* x, const void* Wf, int32_t dtype, co
     // that block b's tiles and block b + 8's are a row tile's two halves
     const int64_t g = std::min<int64_t>(ntiles, std::max(16, cus / 16 * 16));
     hipStream_t st = as_stream(stream);
-    auto go = [&](auto e_tag, auto m_tag) {
-        using E = decltype(e_tag);
-        auto kern = linear512_relu_kernel<E, decltype(m_tag)::value>;
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLLds);
-        hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(512), kLLds, st, M, (const E*)x, (const frag8*)Wf, (E*)y,
-                           (int)ntiles, (int)nrt, (const E*)mask);
+    auto go = [&](const char* what, auto m_tag) {
+        return dispatch_dtype<AVR_DTYPE_F16, AVR_DTYPE_BF16>(dtype, what, [&](auto e_tag) {
+            using E = typename decltype(e_tag)::type;
+            return launch(what, linear512_relu_kernel<E, decltype(m_tag)::value>, dim3((unsigned)g), dim3(512), kLLds,
+                          st, M, (const E*)x, (const frag8*)Wf, (E*)y, (int)ntiles, (int)nrt, (const E*)mask);
+        });
     };
 #ifdef AVR_SHAPE_PROBES
-    if (!mask) {
-        if (dtype == AVR_DTYPE_F16)
-            go(__half{}, std::false_type{});
-        else
-            go(__hip_bfloat16{}, std::false_type{});
-        return check_launch("avr_linear512_relu_fwd");
-    }
+    if (!mask) return go("avr_linear512_relu_fwd", std::false_type{});
 #endif
     AVR_REQUIRE(mask != nullptr, "avr_linear512: mask required");
-    if (dtype == AVR_DTYPE_F16)
-        go(__half{}, std::true_type{});
-    else
-        go(__hip_bfloat16{}, std::true_type{});
-    return check_launch("avr_linear512_mask_fwd");
+    return go("avr_linear512_mask_fwd", std::true_type{});
 }
 }  // namespace
 

@@ -229,9 +229,8 @@ extern "C" int avr_linear_pack_w(int32_t N, int32_t K, const void* W, int32_t dt
                 "avr_linear_pack_w: W and Wf must be 16-byte aligned");
     const int64_t n = (int64_t)(N / 32) * kLKS * 64;
     const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(linear_pack_w_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), (const uint16_t*)W,
-                       (frag8*)Wf, n);
-    return check_launch("avr_linear_pack_w");
+    return launch("avr_linear_pack_w", linear_pack_w_kernel, dim3(blocks), dim3(256), 0, as_stream(stream),
+                  (const uint16_t*)W, (frag8*)Wf, n);
 }
 
 extern "C" int avr_linear_relu_fwd(int64_t M, int32_t N, int32_t K, const void* x, const void* Wf, int32_t dtype,
@@ -248,20 +247,14 @@ extern "C" int avr_linear_relu_fwd(int64_t M, int32_t N, int32_t K, const void* 
     const int64_t items = (M + rows - 1) / rows;
     AVR_REQUIRE(items < (1ll << 31), "avr_linear_relu_fwd: too many rows");
     hipStream_t st = as_stream(stream);
-    auto run = [&](auto e_tag) {
-        using E = decltype(e_tag);
+    return dispatch_dtype<AVR_DTYPE_F16, AVR_DTYPE_BF16>(dtype, "avr_linear_relu_fwd", [&](auto e_tag) {
+        using E = typename decltype(e_tag)::type;
         auto go = [&](auto kern, int waves, size_t lds) {
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(kern, dim3((unsigned)items), dim3(64 * waves), lds, st, M, (int)N, (const E*)x,
-                               (const frag8*)Wf, (E*)y, (int)relu);
+            return launch("avr_linear_relu_fwd", kern, dim3((unsigned)items), dim3(64 * waves), lds, st, M, (int)N,
+                          (const E*)x, (const frag8*)Wf, (E*)y, (int)relu);
         };
-        if (shape == 0) go(linear_xs_kernel<E, 32, 4, 2>, 4, 2 * (size_t)kLTile);
-        else if (shape == 1) go(linear_xs_kernel<E, 64, 8, 2>, 8, 4 * (size_t)kLTile);
-        else go(linear_xs_kernel<E, 32, 8, 4>, 8, 4 * (size_t)kLTile);
-    };
-    if (dtype == AVR_DTYPE_F16)
-        run(__half{});
-    else
-        run(__hip_bfloat16{});
-    return check_launch("avr_linear_relu_fwd");
+        if (shape == 0) return go(linear_xs_kernel<E, 32, 4, 2>, 4, 2 * (size_t)kLTile);
+        if (shape == 1) return go(linear_xs_kernel<E, 64, 8, 2>, 8, 4 * (size_t)kLTile);
+        return go(linear_xs_kernel<E, 32, 8, 4>, 8, 4 * (size_t)kLTile);
+    });
 }

@@ -445,20 +445,19 @@ extern "C" int avr_metrics(int32_t B, int32_t n, double fs, int32_t s50, int32_t
     const int K = n / 2 + 1;
     const float2* tw = reinterpret_cast<const float2*>(ir_twiddle);
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(met_dft_kernel, dim3((K + kT - 1) / kT, 2 * B), dim3(kT), 0, st, B, n, ori, pred,
-                       tw, W.X);
-    if (int e = check_launch("met_dft_kernel")) return e;
-    hipLaunchKernelGGL(met_hilbert_kernel, dim3((n + kT - 1) / kT, 2 * B), dim3(kT), 0, st, B, n, ori,
-                       pred, tw, W.X, W.env);
-    if (int e = check_launch("met_hilbert_kernel")) return e;
-    hipLaunchKernelGGL(met_energy_kernel, dim3(B, 2), dim3(kT), 0, st, B, n, fs, s50, ori, pred, rows,
-                       ori_energy, pred_energy);
-    if (int e = check_launch("met_energy_kernel")) return e;
-    hipLaunchKernelGGL(met_pair_kernel, dim3(B), dim3(kT), 0, st, B, n, window, W.X, W.env, rows);
-    if (int e = check_launch("met_pair_kernel")) return e;
+    if (int e = launch("met_dft_kernel", met_dft_kernel, dim3((K + kT - 1) / kT, 2 * B), dim3(kT), 0, st, B, n, ori,
+                       pred, tw, W.X))
+        return e;
+    if (int e = launch("met_hilbert_kernel", met_hilbert_kernel, dim3((n + kT - 1) / kT, 2 * B), dim3(kT), 0, st, B,
+                       n, ori, pred, tw, W.X, W.env))
+        return e;
+    if (int e = launch("met_energy_kernel", met_energy_kernel, dim3(B, 2), dim3(kT), 0, st, B, n, fs, s50, ori, pred,
+                       rows, ori_energy, pred_energy))
+        return e;
+    if (int e = launch("met_pair_kernel", met_pair_kernel, dim3(B), dim3(kT), 0, st, B, n, window, W.X, W.env, rows))
+        return e;
     // auraloss is called as (ori, pred): the criterion's argument order
     if (int e = launch_mr3(B, n, pred, ori, win_table, tw512, W.mr, W.mr_bytes, means + 6, stream))
         return e;
-    hipLaunchKernelGGL(met_final_kernel, dim3(1), dim3(64), 0, st, B, n, rows, means);
-    return check_launch("met_final_kernel");
+    return launch("met_final_kernel", met_final_kernel, dim3(1), dim3(64), 0, st, B, n, rows, means);
 }

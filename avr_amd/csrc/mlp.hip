@@ -496,16 +496,17 @@ extern "C" int avr_linear_wgrad(int64_t N, int32_t M, int32_t K, const void* gra
     // all tiles of a split on one XCD (its rows re-read from that L2): block
     // b runs on XCD b % 8, split = b % 8 + 8 * (b / 8 / tiles)
     const int64_t blocks = (int64_t)tiles * ((used + 7) / 8 * 8);
-    hipLaunchKernelGGL(linear_wgrad_dma_kernel, dim3((unsigned)blocks), dim3(256), 0, st, N, (int)M, (int)K, rows,
-                       used, (const __hip_bfloat16*)grad_y, (const __hip_bfloat16*)x, workspace);
-    if (int e = check_launch("avr_linear_wgrad")) return e;
+    if (int e = launch("avr_linear_wgrad", linear_wgrad_dma_kernel, dim3((unsigned)blocks), dim3(256), 0, st, N,
+                       (int)M, (int)K, rows, used, (const __hip_bfloat16*)grad_y, (const __hip_bfloat16*)x,
+                       workspace))
+        return e;
     const int64_t MK = (int64_t)M * K;
     int G = 1;
     while (G < 64 && 2 * G <= used && (MK / 4) * G < 131072) G *= 2;
     const int64_t quads_per_block = 256 / G;
-    hipLaunchKernelGGL(wgrad_finalize_kernel, dim3((unsigned)((MK / 4 + quads_per_block - 1) / quads_per_block)),
-                       dim3(256), 0, st, MK, used, G, workspace, grad_w);
-    return check_launch("avr_linear_wgrad_finalize");
+    return launch("avr_linear_wgrad_finalize", wgrad_finalize_kernel,
+                  dim3((unsigned)((MK / 4 + quads_per_block - 1) / quads_per_block)), dim3(256), 0, st, MK, used, G,
+                  workspace, grad_w);
 }
 
 namespace {
@@ -526,13 +527,11 @@ extern "C" int avr_linear_out1_fwd(int64_t N, int32_t K, const void* x, const vo
     const int64_t threads = N * (K / 8);
     const dim3 grid((unsigned)((threads + 255) / 256));
     hipStream_t st = as_stream(stream);
-    if (dtype == AVR_DTYPE_F16)
-        hipLaunchKernelGGL(linear_out1_fwd_kernel<__half>, grid, dim3(256), 0, st, N, (int)K, (const __half*)x,
-                           (const __half*)w, (__half*)y);
-    else
-        hipLaunchKernelGGL(linear_out1_fwd_kernel<__hip_bfloat16>, grid, dim3(256), 0, st, N, (int)K,
-                           (const __hip_bfloat16*)x, (const __hip_bfloat16*)w, (__hip_bfloat16*)y);
-    return check_launch("avr_linear_out1_fwd");
+    return dispatch_dtype<AVR_DTYPE_F16, AVR_DTYPE_BF16>(dtype, "avr_linear_out1_fwd", [&](auto tag) {
+        using E = typename decltype(tag)::type;
+        return launch("avr_linear_out1_fwd", linear_out1_fwd_kernel<E>, grid, dim3(256), 0, st, N, (int)K,
+                      (const E*)x, (const E*)w, (E*)y);
+    });
 }
 
 extern "C" int avr_linear_out1_workspace(int32_t K, int64_t* floats) {
@@ -551,20 +550,18 @@ extern "C" int avr_linear_out1_bwd(int64_t N, int32_t K, const void* x, const vo
     const int64_t rows = (N + kOut1Blocks - 1) / kOut1Blocks;
     const int used = (int)((N + rows - 1) / rows);
     hipStream_t st = as_stream(stream);
-    if (dtype == AVR_DTYPE_F16)
-        hipLaunchKernelGGL(linear_out1_bwd_kernel<__half>, dim3(used), dim3(256), 0, st, N, (int)K, rows,
-                           (const __half*)x, (const __half*)w, (const __half*)grad_y, (__half*)grad_x, workspace);
-    else
-        hipLaunchKernelGGL(linear_out1_bwd_kernel<__hip_bfloat16>, dim3(used), dim3(256), 0, st, N, (int)K, rows,
-                           (const __hip_bfloat16*)x, (const __hip_bfloat16*)w, (const __hip_bfloat16*)grad_y,
-                           (__hip_bfloat16*)grad_x, workspace);
-    if (int e = check_launch("avr_linear_out1_bwd")) return e;
+    if (int e = dispatch_dtype<AVR_DTYPE_F16, AVR_DTYPE_BF16>(dtype, "avr_linear_out1_bwd", [&](auto tag) {
+            using E = typename decltype(tag)::type;
+            return launch("avr_linear_out1_bwd", linear_out1_bwd_kernel<E>, dim3(used), dim3(256), 0, st, N, (int)K,
+                          rows, (const E*)x, (const E*)w, (const E*)grad_y, (E*)grad_x, workspace);
+        }))
+        return e;
     int G = 1;
     while (G < 64 && 2 * G <= used && (K / 4) * G < 131072) G *= 2;
     const int64_t quads_per_block = 256 / G;
-    hipLaunchKernelGGL(wgrad_finalize_kernel, dim3((unsigned)((K / 4 + quads_per_block - 1) / quads_per_block)),
-                       dim3(256), 0, st, (int64_t)K, used, G, workspace, grad_w);
-    return check_launch("avr_linear_out1_finalize");
+    return launch("avr_linear_out1_finalize", wgrad_finalize_kernel,
+                  dim3((unsigned)((K / 4 + quads_per_block - 1) / quads_per_block)), dim3(256), 0, st, (int64_t)K,
+                  used, G, workspace, grad_w);
 }
 
 extern "C" int avr_narrow_mm(int64_t N, int32_t R, int32_t C, const void* X, const void* Bt, int32_t dtype,
@@ -587,7 +584,7 @@ extern "C" int avr_narrow_mm(int64_t N, int32_t R, int32_t C, const void* X, con
     const size_t x_lds = (size_t)kNarrowRows * (R / 8 + 1) * 16;
     const bool stage = AVR_NARROW_STAGE && bt_lds + x_lds <= 80 * 1024;
     auto go = [&](auto e_tag, auto n_tag, auto a_tag) {
-        using E = decltype(e_tag);
+        using E = typename decltype(e_tag)::type;
         constexpr int kN = decltype(n_tag)::value, kA = decltype(a_tag)::value;
         // (R = 256 only with C <= 128: the 8-tile form would not fit 256 registers)
         constexpr int kN16 = kN == 8 ? 8 : 16;
@@ -598,23 +595,17 @@ extern "C" int avr_narrow_mm(int64_t N, int32_t R, int32_t C, const void* X, con
         };
         auto kern = stage ? pick(std::true_type{}) : pick(std::false_type{});
         const size_t lds = bt_lds + (stage ? x_lds : 0);
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, N, (int)R, (int)C, (const E*)X,
-                           (const E*)Bt, (const E*)mask, (E*)Y);
+        return launch("avr_narrow_mm", kern, dim3((unsigned)grid), dim3(256), lds, st, N, (int)R, (int)C,
+                      (const E*)X, (const E*)Bt, (const E*)mask, (E*)Y);
     };
     auto by_act = [&](auto e_tag, auto n_tag) {
-        if (act == 0) go(e_tag, n_tag, std::integral_constant<int, 0>{});
-        else if (act == 1) go(e_tag, n_tag, std::integral_constant<int, 1>{});
-        else go(e_tag, n_tag, std::integral_constant<int, 2>{});
+        if (act == 0) return go(e_tag, n_tag, std::integral_constant<int, 0>{});
+        if (act == 1) return go(e_tag, n_tag, std::integral_constant<int, 1>{});
+        return go(e_tag, n_tag, std::integral_constant<int, 2>{});
     };
-    auto by_n = [&](auto e_tag) {
-        if (nct == 3) by_act(e_tag, std::integral_constant<int, 3>{});
-        else if (nct == 4) by_act(e_tag, std::integral_constant<int, 4>{});
-        else by_act(e_tag, std::integral_constant<int, 8>{});
-    };
-    if (dtype == AVR_DTYPE_F16)
-        by_n(__half{});
-    else
-        by_n(__hip_bfloat16{});
-    return check_launch("avr_narrow_mm");
+    return dispatch_dtype<AVR_DTYPE_F16, AVR_DTYPE_BF16>(dtype, "avr_narrow_mm", [&](auto e_tag) {
+        if (nct == 3) return by_act(e_tag, std::integral_constant<int, 3>{});
+        if (nct == 4) return by_act(e_tag, std::integral_constant<int, 4>{});
+        return by_act(e_tag, std::integral_constant<int, 8>{});
+    });
 }

@@ -356,9 +356,8 @@ extern "C" int avr_mlp512x2_pack_w(const void* W1, const void* W2, int32_t dtype
                     reinterpret_cast<uintptr_t>(Wf) % 16 == 0,
                 "avr_mlp512x2_pack_w: W1, W2 and Wf must be 16-byte aligned");
     const int64_t n = (int64_t)kMN * (kMPair / 16);  // fragments of both layers
-    hipLaunchKernelGGL(mlp512_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream),
-                       (const uint16_t*)W1, (const uint16_t*)W2, (frag8*)Wf, n);
-    return check_launch("avr_mlp512x2_pack_w");
+    return launch("avr_mlp512x2_pack_w", mlp512_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                  as_stream(stream), (const uint16_t*)W1, (const uint16_t*)W2, (frag8*)Wf, n);
 }
 
 extern "C" int avr_mlp512x2_fwd(int64_t M, const void* x, const void* Wf, int32_t dtype, void* y, void* stream) {
@@ -373,16 +372,9 @@ extern "C" int avr_mlp512x2_fwd(int64_t M, const void* x, const void* Wf, int32_
     const int grid = (int)std::min<int64_t>(items, std::max(cus, 1));
     const size_t lds = 2 * (size_t)kMPair + (AVR_MLP_TSTORE ? 4 * 4096 : 0);
     hipStream_t st = as_stream(stream);
-    auto go = [&](auto e_tag) {
-        using E = decltype(e_tag);
-        auto kern = mlp512x2_kernel<E>;
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, M, (const E*)x, (const frag8*)Wf, (E*)y,
-                           (int)items);
-    };
-    if (dtype == AVR_DTYPE_F16)
-        go(__half{});
-    else
-        go(__hip_bfloat16{});
-    return check_launch("avr_mlp512x2_fwd");
+    return dispatch_dtype<AVR_DTYPE_F16, AVR_DTYPE_BF16>(dtype, "avr_mlp512x2_fwd", [&](auto e_tag) {
+        using E = typename decltype(e_tag)::type;
+        return launch("avr_mlp512x2_fwd", mlp512x2_kernel<E>, dim3(grid), dim3(256), lds, st, M, (const E*)x,
+                      (const frag8*)Wf, (E*)y, (int)items);
+    });
 }

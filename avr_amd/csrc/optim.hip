@@ -152,11 +152,12 @@ extern "C" int avr_grad_clip_coef(int32_t n_tensors, const float* const* ptrs, c
             n_part += norm_blocks(sizes[base + i]);
             if (norm_blocks(sizes[base + i]) > blocks) blocks = norm_blocks(sizes[base + i]);
         }
-        hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)blocks, cnt), dim3(kNormThreads), 0, st, tab, part);
-        if (int e = check_launch("avr_grad_clip_coef")) return e;
+        if (int e = launch("avr_grad_clip_coef", grad_sumsq_kernel, dim3((unsigned)blocks, cnt), dim3(kNormThreads), 0,
+                           st, tab, part))
+            return e;
     }
-    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(1024), 0, st, part, n_part, max_norm, total, coef);
-    return check_launch("avr_grad_clip_coef");
+    return launch("avr_grad_clip_coef", clip_coef_kernel, dim3(1), dim3(1024), 0, st, part, n_part, max_norm, total,
+                  coef);
 }
 
 extern "C" int avr_scale_sanitize(int32_t n_tensors, float* const* ptrs, const int64_t* sizes,
@@ -176,9 +177,9 @@ extern "C" int avr_scale_sanitize(int32_t n_tensors, float* const* ptrs, const i
         int64_t blocks = (biggest / 4 + 255) / 256;
         if (blocks > 1024) blocks = 1024;
         if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(scale_sanitize_kernel, dim3((unsigned)blocks, cnt), dim3(256), 0,
-                           as_stream(stream), tab, coef);
-        if (int e = check_launch("avr_scale_sanitize")) return e;
+        if (int e = launch("avr_scale_sanitize", scale_sanitize_kernel, dim3((unsigned)blocks, cnt), dim3(256), 0,
+                           as_stream(stream), tab, coef))
+            return e;
     }
     return 0;
 }
@@ -298,9 +299,9 @@ extern "C" int avr_adam_step(int32_t n_tensors, float* const* params, const floa
         int64_t blocks = (biggest / 4 + 255) / 256;
         if (blocks > 2048) blocks = 2048;
         if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks, cnt), dim3(256), 0, as_stream(stream), tab, hp,
-                           coef);
-        if (int e = check_launch("avr_adam_step")) return e;
+        if (int e = launch("avr_adam_step", adam_kernel, dim3((unsigned)blocks, cnt), dim3(256), 0, as_stream(stream),
+                           tab, hp, coef))
+            return e;
     }
     return 0;
 }

@@ -393,14 +393,9 @@ extern "C" int avr_dft_phase_bwd(const avr_render_params* p, int32_t B, const fl
     const dim3 grid((T + 63) / 64, (S + 15) / 16, B);
     const size_t lds = (size_t)T * sizeof(float2);
     (void)shift;
-    if (lds > 65536)
-        (void)hipFuncSetAttribute((const void*)dft_phase_bwd_kernel,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(dft_phase_bwd_kernel, grid, dim3(kBwdThreads), lds, as_stream(stream), *p,
-                       reinterpret_cast<const float2*>(grad_out), pl_table,
-                       reinterpret_cast<const float2*>(phase),
-                       reinterpret_cast<const float2*>(twiddle), gz, (int)B, S, T);
-    return check_launch("avr_dft_phase_bwd");
+    return launch("avr_dft_phase_bwd", dft_phase_bwd_kernel, grid, dim3(kBwdThreads), lds, as_stream(stream), *p,
+                  reinterpret_cast<const float2*>(grad_out), pl_table, reinterpret_cast<const float2*>(phase),
+                  reinterpret_cast<const float2*>(twiddle), gz, (int)B, S, T);
 }
 
 namespace {
@@ -434,32 +429,30 @@ int launch_rb(const avr_render_params* p, int B, const void* sig, const float* g
     const int64_t total = (int64_t)B * R * S * T;
     const dim3 grid((R + rps - 1) / rps, groups, B);
     const size_t lds = (size_t)3 * G * max(rps, 1) * 4;
-    const Tin* x = (const Tin*)sig;
-    Tin* gx = (Tin*)gsig;
-    const bool nts = true;  // streaming grad_x stores (profiles/r01_tune_bwd_*.jsonl)
-#define AVR_RB_L(C, GG, MT, NTS)                                                                   \
-    hipLaunchKernelGGL((ray_reduce_bwd_kernel<Tin, VECTOR, C, GG, MT, NTS>), grid, dim3(threads),  \
-                       lds, st, *p, x, gz, w, delay, gx, gw, B, R, S, T, rps, total)
+    // streaming grad_x stores (NTS = true: profiles/r01_tune_bwd_*.jsonl), the
+    // launch bound by the block size
 #define AVR_RB(C, GG)                                                                              \
     if (cpt == C && G == GG) {                                                                     \
-        if (threads <= 512) {                                                                      \
-            if (nts)                                                                               \
-                AVR_RB_L(C, GG, 512, true);                                                        \
-            else                                                                                   \
-                AVR_RB_L(C, GG, 512, false);                                                       \
-        } else {                                                                                   \
-            if (nts)                                                                               \
-                AVR_RB_L(C, GG, 1024, true);                                                       \
-            else                                                                                   \
-                AVR_RB_L(C, GG, 1024, false);                                                      \
-        }                                                                                          \
-        return check_launch("avr_ray_reduce_bwd");                                                 \
+        auto kern = threads <= 512 ? ray_reduce_bwd_kernel<Tin, VECTOR, C, GG, 512, true>          \
+                                   : ray_reduce_bwd_kernel<Tin, VECTOR, C, GG, 1024, true>;        \
+        return launch("avr_ray_reduce_bwd", kern, grid, dim3(threads), lds, st, *p, (const Tin*)sig, gz, w, \
+                      delay, (Tin*)gsig, gw, B, R, S, T, rps, total);                              \
     }
     AVR_RB(1, 1) AVR_RB(1, 2) AVR_RB(1, 4) AVR_RB(2, 1) AVR_RB(2, 2) AVR_RB(2, 4) AVR_RB(3, 1)
     AVR_RB(4, 1)
-#undef AVR_RB_L
 #undef AVR_RB
     return fail(AVR_E_CONFIG, "ray_reduce_bwd: T too long for this build");
+}
+
+// the aligned (16-byte vector) or the element-wise form of one signal dtype
+template <typename Tin>
+int launch_rb_any(const avr_render_params* p, int B, const void* sig, const float* gz, const float* w,
+                  const int32_t* delay, void* gsig, float* gw, hipStream_t st) {
+    const int64_t row = (int64_t)p->n_samples * p->T;
+    if (reinterpret_cast<uintptr_t>(sig) % 16 == 0 && reinterpret_cast<uintptr_t>(gsig) % 16 == 0 &&
+        row % Vec16<Tin>::N == 0)
+        return launch_rb<Tin, true>(p, B, sig, gz, w, delay, gsig, gw, st);
+    return launch_rb<Tin, false>(p, B, sig, gz, w, delay, gsig, gw, st);
 }
 }  // namespace
 
@@ -470,26 +463,11 @@ extern "C" int avr_ray_reduce_bwd(const avr_render_params* p, int32_t B, const v
     AVR_REQUIRE(p && B >= 1 && signal && gz && w && delay && grad_signal && grad_w,
                 "avr_ray_reduce_bwd: bad args");
     AVR_REQUIRE(p->T >= 2 && p->T <= 16384, "avr_ray_reduce_bwd: T out of range");
-    const int64_t st = (int64_t)p->n_samples * p->T;
-    const bool aligned = (reinterpret_cast<uintptr_t>(signal) % 16) == 0 &&
-                         (reinterpret_cast<uintptr_t>(grad_signal) % 16) == 0;
-    hipStream_t s = as_stream(stream);
-    if (sig_dtype == AVR_DTYPE_F32) {
-        if (aligned && st % 4 == 0)
-            return launch_rb<float, true>(p, B, signal, gz, w, delay, grad_signal, grad_w, s);
-        return launch_rb<float, false>(p, B, signal, gz, w, delay, grad_signal, grad_w, s);
-    }
-    if (sig_dtype == AVR_DTYPE_F16) {
-        if (aligned && st % 8 == 0)
-            return launch_rb<__half, true>(p, B, signal, gz, w, delay, grad_signal, grad_w, s);
-        return launch_rb<__half, false>(p, B, signal, gz, w, delay, grad_signal, grad_w, s);
-    }
-    if (sig_dtype == AVR_DTYPE_BF16) {
-        if (aligned && st % 8 == 0)
-            return launch_rb<__hip_bfloat16, true>(p, B, signal, gz, w, delay, grad_signal, grad_w, s);
-        return launch_rb<__hip_bfloat16, false>(p, B, signal, gz, w, delay, grad_signal, grad_w, s);
-    }
-    return fail(AVR_E_ARG, "avr_ray_reduce_bwd: unknown signal dtype");
+    return dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16, AVR_DTYPE_BF16>(
+        sig_dtype, "avr_ray_reduce_bwd", [&](auto tag) {
+            return launch_rb_any<typename decltype(tag)::type>(p, B, signal, gz, w, delay, grad_signal, grad_w,
+                                                              as_stream(stream));
+        });
 }
 
 extern "C" int avr_weights_bwd(const avr_render_params* p, int32_t B, const void* attn,
@@ -502,29 +480,10 @@ extern "C" int avr_weights_bwd(const avr_render_params* p, int32_t B, const void
     const int64_t rays = (int64_t)B * n_rays(*p);
     const dim3 grid((unsigned)((rays + wpb - 1) / wpb));
     const size_t lds = (size_t)wpb * 4 * S * sizeof(float);
-    if (lds > 65536) {
-        if (attn_dtype == AVR_DTYPE_F32)
-            (void)hipFuncSetAttribute((const void*)weights_bwd_kernel<float>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        else if (attn_dtype == AVR_DTYPE_F16)
-            (void)hipFuncSetAttribute((const void*)weights_bwd_kernel<__half>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        else
-            (void)hipFuncSetAttribute((const void*)weights_bwd_kernel<__hip_bfloat16>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    if (attn_dtype == AVR_DTYPE_F32)
-        hipLaunchKernelGGL(weights_bwd_kernel<float>, grid, dim3(64 * wpb), lds, as_stream(stream),
-                           *p, (int)B, (const float*)attn, d_vals, grad_w, (float*)grad_attn, wpb);
-    else if (attn_dtype == AVR_DTYPE_F16)
-        hipLaunchKernelGGL(weights_bwd_kernel<__half>, grid, dim3(64 * wpb), lds,
-                           as_stream(stream), *p, (int)B, (const __half*)attn, d_vals, grad_w,
-                           (__half*)grad_attn, wpb);
-    else if (attn_dtype == AVR_DTYPE_BF16)
-        hipLaunchKernelGGL(weights_bwd_kernel<__hip_bfloat16>, grid, dim3(64 * wpb), lds,
-                           as_stream(stream), *p, (int)B, (const __hip_bfloat16*)attn, d_vals, grad_w,
-                           (__hip_bfloat16*)grad_attn, wpb);
-    else
-        return fail(AVR_E_ARG, "avr_weights_bwd: unknown attn dtype");
-    return check_launch("avr_weights_bwd");
+    return dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16, AVR_DTYPE_BF16>(
+        attn_dtype, "avr_weights_bwd", [&](auto tag) {
+            using Ta = typename decltype(tag)::type;
+            return launch("avr_weights_bwd", weights_bwd_kernel<Ta>, grid, dim3(64 * wpb), lds, as_stream(stream),
+                          *p, (int)B, (const Ta*)attn, d_vals, grad_w, (Ta*)grad_attn, wpb);
+        });
 }

@@ -807,24 +807,21 @@ extern "C" int avr_tables(const avr_render_params* p, float* d_vals, float* frac
     if (int e = validate(p)) return e;
     AVR_REQUIRE(d_vals && frac && shift && pl_table && phase && twiddle, "avr_tables: null pointer");
     const int64_t work = (int64_t)p->n_samples * (p->T / 2 + 1);
-    hipLaunchKernelGGL(tables_kernel, dim3(pick_blocks(work, 256, 1024)), dim3(256), 0,
-                       as_stream(stream), *p, d_vals, frac, shift, pl_table,
-                       reinterpret_cast<float2*>(phase), reinterpret_cast<float2*>(twiddle));
-    return check_launch("avr_tables");
+    return launch("avr_tables", tables_kernel, dim3(pick_blocks(work, 256, 1024)), dim3(256), 0,
+                  as_stream(stream), *p, d_vals, frac, shift, pl_table,
+                  reinterpret_cast<float2*>(phase), reinterpret_cast<float2*>(twiddle));
 }
 
 extern "C" int avr_depth_samples(const avr_render_params* p, float* d_vals, void* stream) {
     AVR_REQUIRE(p && p->n_samples >= 1 && d_vals, "avr_depth_samples: bad args");
-    hipLaunchKernelGGL(depth_samples_kernel, dim3((p->n_samples + 255) / 256), dim3(256), 0,
-                       as_stream(stream), *p, d_vals);
-    return check_launch("avr_depth_samples");
+    return launch("avr_depth_samples", depth_samples_kernel, dim3((p->n_samples + 255) / 256), dim3(256), 0,
+                  as_stream(stream), *p, d_vals);
 }
 
 extern "C" int avr_ir_twiddle(int32_t n, float* tw, void* stream) {
     AVR_REQUIRE(n >= 2 && tw, "avr_ir_twiddle: bad args");
-    hipLaunchKernelGGL(ir_twiddle_kernel, dim3(pick_blocks(n, 256, 256)), dim3(256), 0,
-                       as_stream(stream), n, reinterpret_cast<float2*>(tw));
-    return check_launch("avr_ir_twiddle");
+    return launch("avr_ir_twiddle", ir_twiddle_kernel, dim3(pick_blocks(n, 256, 256)), dim3(256), 0,
+                  as_stream(stream), n, reinterpret_cast<float2*>(tw));
 }
 
 extern "C" int avr_ray_directions(const avr_render_params* p, const float* u_azi, float* dirs,
@@ -832,9 +829,8 @@ extern "C" int avr_ray_directions(const avr_render_params* p, const float* u_azi
     if (int e = validate(p)) return e;
     AVR_REQUIRE(u_azi && dirs, "avr_ray_directions: null pointer");
     const int R = grid_rays(*p);
-    hipLaunchKernelGGL(ray_directions_kernel, dim3((R + 255) / 256), dim3(256), 0,
-                       as_stream(stream), *p, u_azi, dirs);
-    return check_launch("avr_ray_directions");
+    return launch("avr_ray_directions", ray_directions_kernel, dim3((R + 255) / 256), dim3(256), 0,
+                  as_stream(stream), *p, u_azi, dirs);
 }
 
 extern "C" int avr_sample_points(const avr_render_params* p, int32_t B, const float* rays_o,
@@ -846,10 +842,9 @@ extern "C" int avr_sample_points(const avr_render_params* p, int32_t B, const fl
                 "avr_sample_points: bad args");
     AVR_REQUIRE(!dir_tx || net_dir_tx, "avr_sample_points: dir_tx given without net_dir_tx");
     const int64_t n = (int64_t)B * n_rays(*p) * p->n_samples;
-    hipLaunchKernelGGL(sample_points_kernel, dim3(pick_blocks(n, 256, 8192)), dim3(256), 0,
-                       as_stream(stream), *p, (int)B, rays_o, pos_tx, dir_tx, dirs, d_vals,
-                       net_pts, net_view, net_tx, dir_tx ? net_dir_tx : nullptr);
-    return check_launch("avr_sample_points");
+    return launch("avr_sample_points", sample_points_kernel, dim3(pick_blocks(n, 256, 8192)), dim3(256), 0,
+                  as_stream(stream), *p, (int)B, rays_o, pos_tx, dir_tx, dirs, d_vals,
+                  net_pts, net_view, net_tx, dir_tx ? net_dir_tx : nullptr);
 }
 
 extern "C" int avr_sample_rays(const avr_render_params* p, int32_t B, const float* u_azi_host,
@@ -866,12 +861,11 @@ extern "C" int avr_sample_rays(const avr_render_params* p, int32_t B, const floa
     AziJitter jit;
     for (int i = 0; i < AVR_MAX_AZI; ++i) jit.u[i] = (i < p->n_azi) ? u_azi_host[i] : 0.0f;
     const int64_t n = (int64_t)B * n_rays(*p) * p->n_samples;
-    hipLaunchKernelGGL(sample_rays_kernel, dim3((unsigned)((n + kSampleThreads - 1) / kSampleThreads)),
-                       dim3(kSampleThreads), 0,
-                       as_stream(stream), *p, (int)B, jit, (const float*)nullptr, (int)ray_begin, rays_o,
-                       pos_tx, dir_tx, dirs, net_pts, net_view, net_tx, dir_tx ? net_dir_tx : nullptr,
-                       (float*)nullptr);
-    return check_launch("avr_sample_rays");
+    return launch("avr_sample_rays", sample_rays_kernel,
+                  dim3((unsigned)((n + kSampleThreads - 1) / kSampleThreads)), dim3(kSampleThreads), 0,
+                  as_stream(stream), *p, (int)B, jit, (const float*)nullptr, (int)ray_begin, rays_o,
+                  pos_tx, dir_tx, dirs, net_pts, net_view, net_tx, dir_tx ? net_dir_tx : nullptr,
+                  (float*)nullptr);
 }
 
 // Same launch with the jitter read from DEVICE memory when the kernel runs
@@ -888,11 +882,10 @@ extern "C" int avr_sample_rays_dev(const avr_render_params* p, int32_t B, const 
                 "avr_sample_rays_dev: ray range outside the sphere");
     AziJitter jit{};
     const int64_t n = (int64_t)B * n_rays(*p) * p->n_samples;
-    hipLaunchKernelGGL(sample_rays_kernel, dim3((unsigned)((n + kSampleThreads - 1) / kSampleThreads)),
-                       dim3(kSampleThreads), 0,
-                       as_stream(stream), *p, (int)B, jit, u_azi_dev, (int)ray_begin, rays_o, pos_tx, dir_tx,
-                       dirs, net_pts, net_view, net_tx, dir_tx ? net_dir_tx : nullptr, (float*)nullptr);
-    return check_launch("avr_sample_rays_dev");
+    return launch("avr_sample_rays_dev", sample_rays_kernel,
+                  dim3((unsigned)((n + kSampleThreads - 1) / kSampleThreads)), dim3(kSampleThreads), 0,
+                  as_stream(stream), *p, (int)B, jit, u_azi_dev, (int)ray_begin, rays_o, pos_tx, dir_tx,
+                  dirs, net_pts, net_view, net_tx, dir_tx ? net_dir_tx : nullptr, (float*)nullptr);
 }
 
 extern "C" int avr_sample_rays_staged(const avr_render_params* p, int32_t B, const float* staged,
@@ -911,10 +904,10 @@ extern "C" int avr_sample_rays_staged(const avr_render_params* p, int32_t B, con
     const float* dtx = has_dir_tx ? tx + 3 * B : nullptr;
     const float* u = staged + 9 * B;
     const int64_t n = (int64_t)B * n_rays(*p) * p->n_samples;
-    hipLaunchKernelGGL(sample_rays_kernel, dim3((unsigned)((n + kSampleThreads - 1) / kSampleThreads)),
-                       dim3(kSampleThreads), 0, as_stream(stream), *p, (int)B, jit, u, (int)ray_begin,
-                       ro, tx, dtx, dirs, net_pts, net_view, net_tx, dtx ? net_dir_tx : nullptr, pose_out);
-    return check_launch("avr_sample_rays_staged");
+    return launch("avr_sample_rays_staged", sample_rays_kernel,
+                  dim3((unsigned)((n + kSampleThreads - 1) / kSampleThreads)), dim3(kSampleThreads), 0,
+                  as_stream(stream), *p, (int)B, jit, u, (int)ray_begin, ro, tx, dtx, dirs, net_pts, net_view,
+                  net_tx, dtx ? net_dir_tx : nullptr, pose_out);
 }
 
 extern "C" int avr_weights_fwd(const avr_render_params* p, int32_t B, const void* attn,
@@ -927,35 +920,18 @@ extern "C" int avr_weights_fwd(const avr_render_params* p, int32_t B, const void
     const int64_t rays = (int64_t)B * n_rays(*p);
     const dim3 grid((unsigned)((rays + 3) / 4));
     const size_t lds = 4 * (size_t)p->n_samples * sizeof(float);
-    if (lds > 65536) {
-        (void)hipFuncSetAttribute((const void*)weights_fwd_kernel<float>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)weights_fwd_kernel<__half>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)weights_fwd_kernel<__hip_bfloat16>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    if (attn_dtype == AVR_DTYPE_F32)
-        hipLaunchKernelGGL(weights_fwd_kernel<float>, grid, dim3(256), lds, as_stream(stream), *p,
-                           (int)B, (const float*)attn, rays_o, pos_tx, dirs, d_vals, w, delay);
-    else if (attn_dtype == AVR_DTYPE_F16)
-        hipLaunchKernelGGL(weights_fwd_kernel<__half>, grid, dim3(256), lds, as_stream(stream),
-                           *p, (int)B, (const __half*)attn, rays_o, pos_tx, dirs, d_vals, w, delay);
-    else if (attn_dtype == AVR_DTYPE_BF16)
-        hipLaunchKernelGGL(weights_fwd_kernel<__hip_bfloat16>, grid, dim3(256), lds,
-                           as_stream(stream), *p, (int)B, (const __hip_bfloat16*)attn, rays_o,
-                           pos_tx, dirs, d_vals, w, delay);
-    else
-        return fail(AVR_E_ARG, "avr_weights_fwd: unknown attn dtype");
-    return check_launch("avr_weights_fwd");
+    return dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16, AVR_DTYPE_BF16>(
+        attn_dtype, "avr_weights_fwd", [&](auto tag) {
+            using Ta = typename decltype(tag)::type;
+            return launch("avr_weights_fwd", weights_fwd_kernel<Ta>, grid, dim3(256), lds, as_stream(stream), *p,
+                          (int)B, (const Ta*)attn, rays_o, pos_tx, dirs, d_vals, w, delay);
+        });
 }
 
-
 namespace {
-// Streaming variant of the reduction: 4 rows in flight per lane with
-// non-temporal loads, the best of the sweeps (profiles/r01_tune*; 8 rows is
-// variant 3).
-int reduce_variant() { return 2; }
+// Rows in flight per lane of the streaming reduction (non-temporal loads):
+// the best of the sweeps (profiles/r01_tune*; 8 rows was slower).
+constexpr int kReduceRows = 4;
 
 struct ReduceShape {
     int G, cpt, threads;
@@ -981,31 +957,6 @@ ReduceShape reduce_shape(int S, int T) {
     return sh;
 }
 
-// Variants: rows in flight per lane (4 or 8) x launch
-// bound (512 threads leaves 256 VGPRs per lane, 1024 only 128).
-template <typename Tin, bool VECTOR, int C, int G>
-void launch_reduce_v(dim3 grid, dim3 block, size_t lds, hipStream_t st, const avr_render_params& pp,
-                     const Tin* s, const float* w,
-                     const int32_t* delay, float* part, int B, int R, int S, int T, int rps,
-                     int64_t total) {
-    const bool u8 = reduce_variant() == 3;
-    if (block.x <= 512) {
-        if (u8)
-            hipLaunchKernelGGL((ray_reduce_fwd_kernel<Tin, VECTOR, C, 8, G, 512>), grid, block,
-                               lds, st, pp, s, w, delay, part, B, R, S, T, rps, total);
-        else
-            hipLaunchKernelGGL((ray_reduce_fwd_kernel<Tin, VECTOR, C, 4, G, 512>), grid, block,
-                               lds, st, pp, s, w, delay, part, B, R, S, T, rps, total);
-    } else {
-        if (u8)
-            hipLaunchKernelGGL((ray_reduce_fwd_kernel<Tin, VECTOR, C, 8, G, 1024>), grid, block,
-                               lds, st, pp, s, w, delay, part, B, R, S, T, rps, total);
-        else
-            hipLaunchKernelGGL((ray_reduce_fwd_kernel<Tin, VECTOR, C, 4, G, 1024>), grid, block,
-                               lds, st, pp, s, w, delay, part, B, R, S, T, rps, total);
-    }
-}
-
 template <typename Tin, bool VECTOR>
 int launch_reduce(const avr_render_params* p, int B, const void* sig, const float* w,
                   const int32_t* delay, int n_split, float* part, hipStream_t st) {
@@ -1019,16 +970,32 @@ int launch_reduce(const avr_render_params* p, int B, const void* sig, const floa
     const dim3 grid(n_split, (S + sh.G - 1) / sh.G, B);
     const dim3 block(sh.threads);
     const size_t lds = (size_t)sh.G * max(rps, 1) * 8;
-    const Tin* s = (const Tin*)sig;
-#define AVR_RR(C, GG)                                                                              \
-    if (sh.cpt == C && sh.G == GG)                                                                 \
-        return launch_reduce_v<Tin, VECTOR, C, GG>(grid, block, lds, st, *p, s, w, delay, part, B, R, S, \
-                                                   T, rps, total),                                 \
-               check_launch("avr_ray_reduce_fwd");
-    AVR_RR(1, 1) AVR_RR(1, 2) AVR_RR(1, 4) AVR_RR(2, 1) AVR_RR(2, 2) AVR_RR(2, 4) AVR_RR(3, 1)
-    AVR_RR(4, 1)
-#undef AVR_RR
+    // chunks per lane (template) x launch bound (512 threads leave 256 VGPRs
+    // per lane, 1024 only 128); reduce_shape() gives G = 1 and cpt <= 4
+    auto go = [&](auto c_tag) {
+        constexpr int C = decltype(c_tag)::value;
+        auto kern = block.x <= 512 ? ray_reduce_fwd_kernel<Tin, VECTOR, C, kReduceRows, 1, 512>
+                                   : ray_reduce_fwd_kernel<Tin, VECTOR, C, kReduceRows, 1, 1024>;
+        return launch("avr_ray_reduce_fwd", kern, grid, block, lds, st, *p, (const Tin*)sig, w, delay, part, B, R, S,
+                      T, rps, total);
+    };
+    if (sh.G == 1) switch (sh.cpt) {
+            case 1: return go(std::integral_constant<int, 1>{});
+            case 2: return go(std::integral_constant<int, 2>{});
+            case 3: return go(std::integral_constant<int, 3>{});
+            case 4: return go(std::integral_constant<int, 4>{});
+        }
     return fail(AVR_E_CONFIG, "ray_reduce: T too long for this build");
+}
+
+// the aligned (16-byte vector) or the element-wise form of one signal dtype
+template <typename Tin>
+int launch_reduce_any(const avr_render_params* p, int B, const void* sig, const float* w, const int32_t* delay,
+                      int n_split, float* part, hipStream_t st) {
+    const int64_t row = (int64_t)p->n_samples * p->T;
+    if (reinterpret_cast<uintptr_t>(sig) % 16 == 0 && row % Vec16<Tin>::N == 0)
+        return launch_reduce<Tin, true>(p, B, sig, w, delay, n_split, part, st);
+    return launch_reduce<Tin, false>(p, B, sig, w, delay, n_split, part, st);
 }
 }  // namespace
 
@@ -1072,23 +1039,11 @@ extern "C" int avr_ray_reduce_fwd(const avr_render_params* p, int32_t B, const v
     AVR_REQUIRE(n_split >= 1 && n_split <= R, "avr_ray_reduce_fwd: n_split out of range");
     AVR_REQUIRE((R + n_split - 1) / n_split <= kMaxGroupRays,
                 "avr_ray_reduce_fwd: too many rays per split (raise n_split)");
-    const int64_t st = (int64_t)p->n_samples * p->T;
-    const bool aligned = (reinterpret_cast<uintptr_t>(signal) % 16) == 0;
-    hipStream_t s = as_stream(stream);
-    if (sig_dtype == AVR_DTYPE_F32) {
-        if (aligned && st % 4 == 0) return launch_reduce<float, true>(p, B, signal, w, delay, n_split, part, s);
-        return launch_reduce<float, false>(p, B, signal, w, delay, n_split, part, s);
-    }
-    if (sig_dtype == AVR_DTYPE_F16) {
-        if (aligned && st % 8 == 0) return launch_reduce<__half, true>(p, B, signal, w, delay, n_split, part, s);
-        return launch_reduce<__half, false>(p, B, signal, w, delay, n_split, part, s);
-    }
-    if (sig_dtype == AVR_DTYPE_BF16) {
-        if (aligned && st % 8 == 0)
-            return launch_reduce<__hip_bfloat16, true>(p, B, signal, w, delay, n_split, part, s);
-        return launch_reduce<__hip_bfloat16, false>(p, B, signal, w, delay, n_split, part, s);
-    }
-    return fail(AVR_E_ARG, "avr_ray_reduce_fwd: unknown signal dtype");
+    return dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16, AVR_DTYPE_BF16>(
+        sig_dtype, "avr_ray_reduce_fwd", [&](auto tag) {
+            return launch_reduce_any<typename decltype(tag)::type>(p, B, signal, w, delay, n_split, part,
+                                                                  as_stream(stream));
+        });
 }
 
 extern "C" int avr_dft_phase_fwd(const avr_render_params* p, int32_t B, const float* part,
@@ -1111,32 +1066,27 @@ extern "C" int avr_dft_phase_fwd(const avr_render_params* p, int32_t B, const fl
     const dim3 grid((unsigned)(xcd_order ? 8 * ((nst + 7) / 8) * per : nst * per), 1, B);
     const size_t lds = (size_t)T * sizeof(float2);
     auto go = [&](auto kern) {
-        if (lds > 65536)
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lds);
-        hipLaunchKernelGGL(kern, grid, dim3(kDftThreads), lds, as_stream(stream), *p, part, pl_table,
-                           shift, reinterpret_cast<const float2*>(phase),
-                           reinterpret_cast<const float2*>(twiddle),
-                           reinterpret_cast<float2*>(spart), (int)B, S, T, (int)k_split, kchunk, xcd_order);
+        return launch("avr_dft_phase_fwd", kern, grid, dim3(kDftThreads), lds, as_stream(stream), *p, part,
+                      pl_table, shift, reinterpret_cast<const float2*>(phase),
+                      reinterpret_cast<const float2*>(twiddle), reinterpret_cast<float2*>(spart), (int)B, S, T,
+                      (int)k_split, kchunk, xcd_order);
     };
     switch (n_split) {
-        case 1: go(dft_phase_fwd_kernel<1>); break;
-        case 2: go(dft_phase_fwd_kernel<2>); break;
-        case 4: go(dft_phase_fwd_kernel<4>); break;
-        case 8: go(dft_phase_fwd_kernel<8>); break;
-        case 16: go(dft_phase_fwd_kernel<16>); break;
-        default: return fail(AVR_E_ARG, "avr_dft_phase_fwd: n_split must be 1, 2, 4, 8 or 16");
+        case 1: return go(dft_phase_fwd_kernel<1>);
+        case 2: return go(dft_phase_fwd_kernel<2>);
+        case 4: return go(dft_phase_fwd_kernel<4>);
+        case 8: return go(dft_phase_fwd_kernel<8>);
+        case 16: return go(dft_phase_fwd_kernel<16>);
     }
-    return check_launch("avr_dft_phase_fwd");
+    return fail(AVR_E_ARG, "avr_dft_phase_fwd: n_split must be 1, 2, 4, 8 or 16");
 }
 
 extern "C" int avr_spectrum_finalize(int32_t B, int32_t P, int32_t F, const float* spart,
                                      float* out, void* stream) {
     AVR_REQUIRE(B >= 1 && P >= 1 && F >= 1 && spart && out, "avr_spectrum_finalize: bad args");
-    hipLaunchKernelGGL(spectrum_finalize_kernel, dim3((unsigned)((F + 15) / 16), B), dim3(256), 0,
-                       as_stream(stream), (int)B, (int)P, (int)F,
-                       reinterpret_cast<const float2*>(spart), reinterpret_cast<float2*>(out));
-    return check_launch("avr_spectrum_finalize");
+    return launch("avr_spectrum_finalize", spectrum_finalize_kernel, dim3((unsigned)((F + 15) / 16), B), dim3(256),
+                  0, as_stream(stream), (int)B, (int)P, (int)F, reinterpret_cast<const float2*>(spart),
+                  reinterpret_cast<float2*>(out));
 }
 
 namespace avr {
@@ -1147,14 +1097,10 @@ int launch_irfft(int B, int F, const float* spec, const float* spec2, const floa
     AVR_REQUIRE(n <= kIrfftMaxN, "avr_irfft: " AVR_IRFFT_LIMIT_TEXT);
     const size_t lds = irfft_lds(n);
     const int rows = spec2 ? 2 * B : B;
-    if (lds > 65536)
-        (void)hipFuncSetAttribute((const void*)irfft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
-    hipLaunchKernelGGL(irfft_kernel, dim3((n + 31) / 32, rows), dim3(256), lds, as_stream(stream),
-                       (int)F, (int)B, reinterpret_cast<const float2*>(spec),
-                       reinterpret_cast<const float2*>(spec2 ? spec2 : spec),
-                       reinterpret_cast<const float2*>(tw), ir, ir2 ? ir2 : ir);
-    return check_launch("avr_irfft");
+    return launch("avr_irfft", irfft_kernel, dim3((n + 31) / 32, rows), dim3(256), lds, as_stream(stream),
+                  (int)F, (int)B, reinterpret_cast<const float2*>(spec),
+                  reinterpret_cast<const float2*>(spec2 ? spec2 : spec), reinterpret_cast<const float2*>(tw), ir,
+                  ir2 ? ir2 : ir);
 }
 }  // namespace avr
 
@@ -1169,12 +1115,8 @@ extern "C" int avr_irfft_bwd(int32_t B, int32_t F, const float* grad_ir, const f
     const int n = 2 * (F - 1);
     AVR_REQUIRE(n <= kIrfftMaxN, "avr_irfft_bwd: " AVR_IRFFT_LIMIT_TEXT);
     const size_t lds = irfft_bwd_lds(n);
-    if (lds > 65536)
-        (void)hipFuncSetAttribute((const void*)irfft_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
-    hipLaunchKernelGGL(irfft_bwd_kernel, dim3((F + 31) / 32, B), dim3(256), lds, as_stream(stream), (int)F,
-                       grad_ir, reinterpret_cast<const float2*>(tw), reinterpret_cast<float2*>(grad_spec));
-    return check_launch("avr_irfft_bwd");
+    return launch("avr_irfft_bwd", irfft_bwd_kernel, dim3((F + 31) / 32, B), dim3(256), lds, as_stream(stream),
+                  (int)F, grad_ir, reinterpret_cast<const float2*>(tw), reinterpret_cast<float2*>(grad_spec));
 }
 
 // ---------------------------------------------------- one-call render core

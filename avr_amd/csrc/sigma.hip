@@ -690,24 +690,21 @@ template <typename E, int NT, int WAVES, int OCC, int DBG = 0>
 int launch_meshrir(const Args& a, hipStream_t st) {
     const int64_t per_block = 32 * NT * WAVES;
     const dim3 grid((unsigned)((a.N + per_block - 1) / per_block));
-    hipLaunchKernelGGL((sigma_meshrir_kernel<E, NT, WAVES, OCC, DBG>), grid, dim3(64 * WAVES), 0, st, a);
-    return check_launch("avr_sigma_fwd");
+    return launch("avr_sigma_fwd", sigma_meshrir_kernel<E, NT, WAVES, OCC, DBG>, grid, dim3(64 * WAVES), 0, st, a);
 }
 
 template <typename E, int NT, int WAVES, int OCC, int DBG = 0>
 int launch_meshrir_h1(const Args& a, hipStream_t st) {
     const int64_t per_block = 32 * NT * WAVES;
     const dim3 grid((unsigned)((a.N + per_block - 1) / per_block));
-    hipLaunchKernelGGL((sigma_meshrir_h1_kernel<E, NT, WAVES, OCC, DBG>), grid, dim3(64 * WAVES), 0, st, a);
-    return check_launch("avr_sigma_fwd");
+    return launch("avr_sigma_fwd", sigma_meshrir_h1_kernel<E, NT, WAVES, OCC, DBG>, grid, dim3(64 * WAVES), 0, st, a);
 }
 
 template <typename E, int WAVES, int OCC>
 int launch_raf(const Args& a, hipStream_t st) {
     const int64_t per_block = 32 * WAVES;
     const dim3 grid((unsigned)((a.N + per_block - 1) / per_block));
-    hipLaunchKernelGGL((sigma_raf_kernel<E, 1, WAVES, OCC>), grid, dim3(64 * WAVES), 0, st, a);
-    return check_launch("avr_sigma_fwd");
+    return launch("avr_sigma_fwd", sigma_raf_kernel<E, 1, WAVES, OCC>, grid, dim3(64 * WAVES), 0, st, a);
 }
 
 }  // namespace
@@ -775,9 +772,11 @@ extern "C" int avr_sigma_fwd(const avr_sigma_desc* d, const void* wpack, void* b
     a.bias_div = d->bias_div;
     AVR_REQUIRE(d->dtype == AVR_DTYPE_BF16 || d->dtype == AVR_DTYPE_F16,
                 "avr_sigma_fwd: dtype must be AVR_DTYPE_BF16 or AVR_DTYPE_F16");
-    hipStream_t st = as_stream(stream);
-    if (d->dtype == AVR_DTYPE_F16) return dispatch<_Float16>(d, a, h1, two, st);
-    return dispatch<__bf16>(d, a, h1, two, st);
+    return dispatch_dtype<AVR_DTYPE_F16, AVR_DTYPE_BF16>(d->dtype, "avr_sigma_fwd", [&](auto tag) {
+        // the kernels compute in the compiler's native 16-bit types
+        using E = std::conditional_t<std::is_same_v<typename decltype(tag)::type, __half>, _Float16, __bf16>;
+        return dispatch<E>(d, a, h1, two, as_stream(stream));
+    });
 }
 
 namespace {

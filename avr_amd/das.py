@@ -16,6 +16,7 @@ import threading
 import torch
 
 from . import _lib
+from ._lib import _ptr, _stream
 from .renderer import _ir_twiddle
 
 _N_FFT = 512   # criterion.py:43
@@ -23,10 +24,6 @@ _MICS = 8      # criterion.py:41
 _TABLES: dict = {}
 _LOCK = threading.Lock()
 _WS_BYTES = None
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
 
 
 def _steering(dev, fs, speed):
@@ -73,7 +70,7 @@ class _DasFn(torch.autograd.Function):
         nbytes = _ws_bytes()
         ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
         losses = torch.empty(2, dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _stream(dev)
         with torch.cuda.device(dev):
             _lib.call("avr_das_fwd", n, _ptr(pred_time), _ptr(ori_time), _ptr(steer),
                       _ptr(angles), _ptr(tw), ctypes.c_float(beta), ctypes.c_float(w_reg),
@@ -95,7 +92,7 @@ class _DasFn(torch.autograd.Function):
                          (zero if g_ce is None else g_ce.reshape(()).float())])
         steer, angles = _steering(dev, fs, speed)
         grad = torch.empty(_MICS, n, dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _stream(dev)
         with torch.cuda.device(dev):
             _lib.call("avr_das_bwd", n, _ptr(steer), _ptr(angles), _ptr(_ir_twiddle(_N_FFT, dev)),
                       ctypes.c_float(beta), ctypes.c_float(w_reg), ctypes.c_float(w_ce), _ptr(g),

@@ -26,21 +26,13 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import DTYPE_BF16, DTYPE_F16, DTYPE_F32, render_params
+from ._lib import DTYPE_BF16, DTYPE_F16, DTYPE_F32, _ptr, _stream, render_params
 from .options import tuning_env
 from .wcache import cache_lookup, cache_store, capturing, cast_weight
 
 
 _RENDER_KEYS = ("n_samples", "near", "far", "n_azi", "n_ele", "speed", "fs", "pathloss",
                 "xyz_min", "xyz_max")
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 class _NoGuard:
@@ -130,8 +122,6 @@ class Tables:
 
 
 def ctypes_ref(p):
-    import ctypes
-
     return ctypes.byref(p)
 
 
@@ -168,23 +158,20 @@ def check_config(p, tables: Tables):
 # --------------------------------------------------------------------------
 def reduce_splits(p, B, sig_code):
     """Ray splits of the reduction, decided by the library for this shape."""
-    import ctypes
-
     n = ctypes.c_int32(0)
     _lib.call("avr_reduce_splits", ctypes_ref(p), B, sig_code, ctypes.byref(n))
     return int(n.value)
 
 
 def pick_k_split(B, S, T):
-    """t-slices of the DFT GEMM: about 256 workgroups. AVR_KSPLIT overrides."""
-    F = T // 2 + 1
-    nkc = math.ceil(T / 64)
-    forced = tuning_env()[1]
-    forced = int(forced) if forced else None
-    if forced:
-        return max(1, min(nkc, forced))
-    base = math.ceil(F / 128) * math.ceil(S / 32) * B
-    return max(1, min(nkc, math.ceil(256 / max(1, base))))
+    """t-slices of the DFT GEMM for B poses of S samples x T bins, asked of the
+    library (avr_render_core_layout's rule, AVR_KSPLIT included) for callers
+    without Tables; the render paths read the cached Tables.core_layout."""
+    p = _lib.RenderParams(n_azi=1, n_ele=1, n_samples=S, T=T, n_rays=1)
+    off = (ctypes.c_int64 * 5)()
+    sp = (ctypes.c_int32 * 2)()
+    _lib.call("avr_render_core_layout", ctypes_ref(p), B, DTYPE_F32, off, sp)
+    return int(sp[1])
 
 
 # --------------------------------------------------------------------------
@@ -206,7 +193,9 @@ def _spectrum(p, tables, part, n_split, B, dev, st):
     """Partials [n_split, B, S, T] -> DFT + phase -> [B, F, 2]."""
     S, T = p.n_samples, p.T
     F = T // 2 + 1
-    k_split = pick_k_split(B, S, T)
+    # t-slices of the DFT GEMM: the library's rule (AVR_KSPLIT included); it
+    # does not depend on the signal dtype, the partials are fp32
+    k_split = tables.core_layout(p, B, DTYPE_F32)[2]
     P = math.ceil(S / 32) * k_split
     spart = torch.empty(B, P, F, 2, dtype=torch.float32, device=dev)
     _lib.call("avr_dft_phase_fwd", ctypes_ref(p), B, _ptr(part), n_split, _ptr(tables.pl),

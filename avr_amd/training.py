@@ -21,11 +21,8 @@ import torch
 from torch.autograd.graph import increment_version
 
 from . import _lib
+from ._lib import _stream
 from .criterion import Criterion
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def _clip_coef(grads, max_norm):

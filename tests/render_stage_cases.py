@@ -104,7 +104,7 @@ class DftCase:
     S: int
     T: int
     n_splits: tuple = (1,)
-    k_splits: tuple = ()  # forced values besides pick_k_split's; "max" = ceil(T/64)
+    k_splits: tuple = ()  # forced values besides the library's; "max" = ceil(T/64)
     block: str = "raf"
     B: int = 2
     fwd: bool = True  # backward-only cases (tile tails) set this False

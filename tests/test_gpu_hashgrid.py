@@ -226,6 +226,60 @@ def test_partitioned_backward_set_overwrites(n):
     assert torch.equal(a == 0, b == 0)
 
 
+@pytest.mark.parametrize("log2", [21, 22])
+def test_partitioned_backward_scatter_above_64k_lds(log2):
+    """The scatter pass with more than 64 KiB of dynamic LDS (the launch has
+    to opt in): (3 * 4096 + 3 * partitions + 1) * 4 bytes, with 2048
+    partitions of 1024 entries per level at 2^21 (73,732 B, the smallest table
+    past 64 KiB) and 4096 at 2^22 (98,308 B, the kMaxScatterParts cap).  Two
+    levels at base resolution 256, both hashed at full table size, fp32
+    parameters, 16897 points (the partitioned threshold plus a ragged last
+    chunk), fp16 and fp32 gradients.  The += form into a random base and the
+    = form over NaN equal the atomic kernel within the neighbouring tests'
+    tolerances, and the float64 scatter-add of the restatement within 1e-5 of
+    the gradient's scale."""
+    import ctypes
+
+    from avr_amd import _lib
+    from avr_amd.encoding import _code
+
+    cfg = dict(CFG, n_levels=2, base_resolution=256, log2_hashmap_size=log2)
+    enc = HashGridEncoding(3, cfg, dtype=torch.float32, seed=15).to(DEV)
+    L, n = enc.n_levels, 16897
+    assert list(np.diff(enc._off)) == [1 << log2] * 2  # both levels hashed, full size
+    x_host = _points(n, 16)
+    x = torch.from_numpy(x_host).to(DEV)
+    st = torch.cuda.current_stream(DEV).cuda_stream
+    meta = (enc._off.ctypes.data, enc._scale.ctypes.data, enc._res.ctypes.data)
+    nb = ctypes.c_int64()
+    _lib.call("avr_hashgrid_bwd_workspace", n, L, enc._off.ctypes.data, ctypes.byref(nb))
+    assert nb.value > 256  # the partitioned passes, not the atomic fallback
+    ws = torch.empty(nb.value, dtype=torch.uint8, device=DEV)
+    base = torch.randn(enc.n_params, device=DEV)
+    for gdtype in (torch.float16, torch.float32):
+        g = torch.randn(n, 2 * L, device=DEV, generator=torch.Generator(device=DEV).manual_seed(17)).to(gdtype)
+        a = torch.zeros(enc.n_params, device=DEV)
+        _lib.call("avr_hashgrid_bwd", n, L, x.data_ptr(), g.data_ptr(), _code(g.dtype), *meta, a.data_ptr(), st)
+        b = base.clone()
+        _lib.call("avr_hashgrid_bwd_partitioned", n, L, x.data_ptr(), g.data_ptr(), _code(g.dtype), *meta,
+                  b.data_ptr(), ws.data_ptr(), nb.value, st)
+        c = torch.full((enc.n_params,), float("nan"), device=DEV)
+        _lib.call("avr_hashgrid_bwd_partitioned_set", n, L, x.data_ptr(), g.data_ptr(), _code(g.dtype), *meta,
+                  c.data_ptr(), ws.data_ptr(), nb.value, st)
+        torch.cuda.synchronize()
+        scale = float(a.abs().max())
+        assert scale > 0
+        assert float((b - base - a).abs().max()) <= 1e-5 * scale + 1e-6
+        assert torch.isfinite(c).all()
+        assert float((c - a).abs().max()) <= 1e-5 * scale
+        assert torch.equal(a == 0, c == 0)
+        ref = hgo.encode_backward(x_host, g.float().cpu().numpy(), enc._off, enc._scale, enc._res, enc.n_params)
+        ref_scale = np.abs(ref).max()
+        err = np.abs(c.double().cpu().numpy() - ref).max() / ref_scale
+        print(f"hashgrid scatter 2^{log2} {gdtype}: workspace {nb.value} B, rel err vs float64 {err:.3e}")
+        assert err < 1e-5, err
+
+
 @pytest.mark.parametrize("dtype", [torch.float16, torch.float32])
 def test_level_major_unit_map_is_bit_identical(dtype):
     """avr_hashgrid_fwd_lm_unit (the (x + 1) / 2 map applied on load) equals

@@ -19,7 +19,7 @@ import render_stage_cases as rsc
 from oracle import avr_oracle as orc
 
 from avr_amd import AVRRender, _lib, spectrum_to_ir
-from avr_amd.renderer import get_tables, pick_k_split, render_params
+from avr_amd.renderer import get_tables, render_params
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
@@ -211,8 +211,14 @@ def _e32_fwd(case, n_split, k_split):
     return rsc.rel_l2(y, o["ref"][:, bins])
 
 
+def _lib_k_split(case):
+    """The k-split the library picks for this shape (avr_render_core_layout)."""
+    p, tb, _ = ctx(case.cfg(), case.T)
+    return tb.core_layout(p, case.B, _lib.DTYPE_F32)[2]
+
+
 def _k_list(case):
-    ks = [pick_k_split(case.B, case.S, case.T)]
+    ks = [_lib_k_split(case)]
     return ks + [k for k in case.forced_k() if k not in ks]
 
 
@@ -274,7 +280,7 @@ def test_dft_phase_bwd(case):
 def test_dft_device_adjointness(case):
     """<fwd(z), g> = <z, bwd(g)> on the device results, in float64, within the
     sum of the two stages' bounds (Cauchy-Schwarz on their relative L2 errors)."""
-    k = pick_k_split(case.B, case.S, case.T)
+    k = _lib_k_split(case)
     out, _, o = _dft_fwd(case, 1, k)
     gz, _ = _dft_bwd(case)
     g = o["g"].astype(np.float64)
