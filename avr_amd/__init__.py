@@ -30,6 +30,13 @@ from .auralize import (  # noqa: F401
     white_noise,
     zero_phase_sos,
 )
+from .doa import (  # noqa: F401
+    das_doa,
+    das_doa_dump,
+    doa_bins,
+    doa_frames,
+    frame_stats,
+)
 from .options import KernelOptions  # noqa: F401
 from . import workloads  # noqa: F401
 

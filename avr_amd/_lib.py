@@ -184,6 +184,12 @@ _SIGS = {
     "avr_sosfiltfilt_workspace": (ctypes.c_int, [_c_i64, _c_i64, _c_i32, _c_i32, _vp]),
     "avr_sosfiltfilt": (ctypes.c_int, [_c_i64, _c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _c_i32, _vp, _c_i32,
                                        _vp, _c_i64, _vp]),
+    "avr_doa_das_workspace": (ctypes.c_int, [_c_i64, _c_i32, _c_i32, _vp]),
+    "avr_doa_das": (ctypes.c_int, [_c_i64, _c_i32, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp, ctypes.c_double,
+                                   _vp, _vp, _c_i32, _vp, _vp, _c_i64, _vp]),
+    "avr_doa_frames": (ctypes.c_int, [_c_i64, _c_i64, _c_i32, _c_i32, _c_i64, _c_i32, _c_i32, _c_i32, _c_i32,
+                                      _c_i32, _c_f32, _vp, _c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "avr_doa_frame_stats": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "avr_sigma_pack_bytes": (ctypes.c_int, [_c_i32, _vp]),
     "avr_sigma_desc_size": (ctypes.c_int, []),
     "avr_sigma_fwd": (ctypes.c_int, [_vp] * 3 + [_c_i32, _vp, _vp]),

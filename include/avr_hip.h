@@ -685,6 +685,49 @@ int avr_sosfiltfilt(int64_t rows, int64_t n, int32_t n_sections, int32_t padlen,
                     const double* zi, const void* y, int32_t in_dtype, void* out, int32_t out_dtype,
                     void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- direction-of-arrival evaluation (csrc/doa.hip) --------
+ * avr_doa_das: plot_eval.py:134-265 run_delay_and_sum_on_npz for G groups of
+ *   8 microphones, predicted and measured IRs together, in three launches.
+ *   pred_ir / ori_ir [G*8][n] fp32 (irfft of the dumped spectra), steer
+ *   [K][8][nfft/2+1] complex64 and angles [K] fp32 (degrees) built by the host
+ *   with the reference's own torch ops, tw [nfft][2] DOUBLES = (cos, -sin)
+ *   (2 pi j / nfft), positions [>= G*8][3] fp32 or fp64.  Every sum on the
+ *   device is fp64 in a fixed order.  out [2][6][G] doubles: method
+ *   (soft-argmax, argmax) x (true_deg, pred_deg, gt_deg, pred_vs_gt_error,
+ *   pred_vs_true_error, gt_vs_true_error).  nfft even in [2, 2048], K <= 1024,
+ *   G <= 32767; the workspace holds avr_doa_das_workspace bytes, 16-byte aligned.
+ *
+ * avr_doa_frames: SRP-PHAT (algo 0), MUSIC (1) or NormMUSIC (2) for one source
+ *   on every frame y[g][:, i*H : i*H + L] of y [G][8][n] (fp32, or fp64 rounded
+ *   to fp32 on load), one launch, one workgroup per (group, frame).  Snapshots
+ *   j < (L - nfft) / hop + 1 of nfft samples, weighted by win [nfft]; bins
+ *   k_lo .. k_lo + K - 1; tw [nfft][2] fp32 = (cos, -sin)(2 pi j / nfft);
+ *   steer [K][8][360] complex64.  est [G][n_frames] int32 (-1 where invalid),
+ *   valid [G][n_frames] bytes, spectrum [G][n_frames][360] fp32 or NULL.  A
+ *   frame with a non-finite sample or no snapshot is invalid.  fp32
+ *   arithmetic in fixed orders, no float atomics.  nfft in [2, 2048].
+ *
+ * avr_doa_frame_stats: whitenoise_bandpass_doa.py:36-49 circ_stats_deg over the
+ *   valid frames of each group (angles in whole degrees, taken modulo 360;
+ *   cos_sin [360][2] doubles = (cos, sin)(deg2rad(d)), a host table with
+ *   numpy's values): out [3][G] doubles (circular mean in degrees,
+ *   1 - R, circular standard deviation in degrees; NaN for a group without a
+ *   valid frame), n_valid [G] int64.
+ *
+ * No call synchronises or copies to the host.  Bad arguments are refused
+ * (AVR_E_ARG) before any device call. */
+int avr_doa_das_workspace(int64_t G, int32_t nfft, int32_t K, int64_t* bytes);
+int avr_doa_das(int64_t G, int32_t n, int32_t nfft, int32_t K, const float* pred_ir,
+                const float* ori_ir, const float* steer, const float* angles, const double* tw,
+                double beta, const void* position_rx, const void* position_tx, int32_t pos_dtype,
+                double* out, void* workspace, int64_t workspace_bytes, void* stream);
+int avr_doa_frames(int64_t G, int64_t n, int32_t L, int32_t H, int64_t n_frames, int32_t nfft,
+                   int32_t hop, int32_t k_lo, int32_t K, int32_t algo, float floor, const void* y,
+                   int32_t y_dtype, const float* tw, const float* win, const float* steer,
+                   int32_t* est, uint8_t* valid, float* spectrum, void* stream);
+int avr_doa_frame_stats(int64_t G, int64_t n_frames, const int32_t* est, const uint8_t* valid,
+                        const double* cos_sin, double* out, int64_t* n_valid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
