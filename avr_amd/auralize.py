@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .criterion import _ptr, _stream
+from ._lib import _ptr, _stream
 
 _DT = {torch.float32: 0, torch.float64: 3}  # AVR_DTYPE_F32, AVR_DTYPE_F64
 MAX_SECTIONS = 8

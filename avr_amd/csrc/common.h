@@ -77,6 +77,31 @@ int launch(const char* what, Kern kern, dim3 grid, dim3 block, size_t lds, hipSt
     return check_launch(what);
 }
 
+// ---------------------------------------------------------------- workspaces
+constexpr int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) & ~(a - 1); }  // a: a power of two
+
+// The one way a workspace is laid out: regions in the order they are taken,
+// each starting at a multiple of `align` bytes from the base.  The same
+// function runs twice, with a null base in the *_workspace entry point (every
+// pointer null, bytes() the size to allocate) and with the caller's pointer in
+// the launcher, so the two agree byte for byte.
+class Arena {
+  public:
+    Arena(void* base, int64_t align) : base_(static_cast<char*>(base)), align_(align) {}
+    template <typename T>
+    T* take(int64_t count) {
+        char* r = base_ ? base_ + off_ : nullptr;
+        off_ += align_up(count * (int64_t)sizeof(T), align_);
+        return reinterpret_cast<T*>(r);
+    }
+    int64_t offset() const { return off_; }  // of the region the next take() returns
+    int64_t bytes() const { return off_; }   // of everything taken
+
+  private:
+    char* base_;
+    int64_t align_, off_ = 0;
+};
+
 // ---------------------------------------------------------------- dtype dispatch
 template <int Code>
 struct dtype_tag;
@@ -249,6 +274,9 @@ __device__ __forceinline__ void store16_nt(T* p, const float* o) {
     using V = Vec16<T>;
     __builtin_nontemporal_store(V::pack(o), reinterpret_cast<typename V::raw*>(p));
 }
+
+// sign(x) as torch.sign: the gradient of |x| (0 at 0)
+__device__ __forceinline__ float sgnf(float x) { return (float)((x > 0.0f) - (x < 0.0f)); }
 
 // ---------------------------------------------------------------- geometry
 // torch.linspace(a, b, n)[i] on CPU: step = (b-a)/(n-1) in fp32, lower half

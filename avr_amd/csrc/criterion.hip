@@ -24,6 +24,7 @@
 // Every sum is in a fixed order: results are deterministic.
 #include <math.h>
 
+#include "block.h"
 #include "common.h"
 
 using namespace avr;
@@ -76,8 +77,6 @@ struct CritWs {
     float* gtime;  // [B][n] d loss / d pred_time
     int64_t bytes;
 };
-
-inline int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
 
 int make_plan(int B, int F, const float* w, CritPlan* P) {
     AVR_REQUIRE(B >= 1 && F >= 2, "avr_criterion: B >= 1 and F >= 2 required");
@@ -132,27 +131,19 @@ int window_len() {
 
 CritWs carve(const CritPlan& P, void* base) {
     CritWs W{};
-    char* p = reinterpret_cast<char*>(base);
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) {
-        char* r = p ? p + o : nullptr;
-        o += align16(bytes);
-        return r;
-    };
+    Arena A(base, 16);
     const int64_t B = P.B;
     const int mr_tiles = P.r[kEnergy].tile_f;
-    W.X = reinterpret_cast<float2*>(take(2 * B * P.NX * (int64_t)sizeof(float2)));
-    W.Y = reinterpret_cast<float*>(take(B * P.NY * 4));
-    W.e = reinterpret_cast<float*>(take(2 * B * P.M4 * 4));
-    W.part = reinterpret_cast<float*>(take(B * mr_tiles * 4 * 4));
-    W.stat = reinterpret_cast<float*>(take(B * 16 * 4));
-    W.ge = reinterpret_cast<float*>(take(B * P.M4 * 4));
-    W.gtime = reinterpret_cast<float*>(take(B * (int64_t)P.n * 4));
-    W.bytes = o;
+    W.X = A.take<float2>(2 * B * P.NX);
+    W.Y = A.take<float>(B * P.NY);
+    W.e = A.take<float>(2 * B * P.M4);
+    W.part = A.take<float>(B * mr_tiles * 4);
+    W.stat = A.take<float>(B * 16);
+    W.ge = A.take<float>(B * P.M4);
+    W.gtime = A.take<float>(B * P.n);
+    W.bytes = A.bytes();
     return W;
 }
-
-__device__ __forceinline__ float sgnf(float x) { return (float)((x > 0.0f) - (x < 0.0f)); }
 
 __device__ __forceinline__ int find_res(const CritPlan& P, int tile, bool fwd) {
     int q = 0;
@@ -168,23 +159,6 @@ __device__ __forceinline__ int reflect(int j, int pad, int n) {
     if (t < 0) t = -t;
     if (t >= n) t = 2 * (n - 1) - t;
     return t;
-}
-
-template <int N>
-__device__ __forceinline__ void block_sum(float (*red)[kThreads], float* v) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int c = 0; c < N; ++c) red[c][tid] = v[c];
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-#pragma unroll
-            for (int c = 0; c < N; ++c) red[c][tid] += red[c][tid + s];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int c = 0; c < N; ++c) v[c] = red[c][0];
 }
 
 // ---------------------------------------------------------------- forward
@@ -260,7 +234,7 @@ __global__ __launch_bounds__(kThreads) void crit_stft_kernel(CritPlan P,
         }
     }
     if (q < kEnergy) {
-        block_sum<4>(red, acc);
+        block_reduce<kThreads, 4>(red, acc, SumOp{});
         if (tid < 4) W.part[((int64_t)b * P.r[kEnergy].tile_f + tile) * 4 + tid] = acc[tid];
     } else {
         __syncthreads();
@@ -330,20 +304,7 @@ __global__ __launch_bounds__(kRedThreads) void crit_reduce_kernel(CritPlan P,
         s[4] += fabsf(sinf(tp) - sinf(to));
     }
     for (int i = tid; i < B * n; i += kRedThreads) s[5] += fabsf(ot[i] - pt[i]);
-#pragma unroll
-    for (int c = 0; c < 6; ++c) red[c][tid] = s[c];
-    __syncthreads();
-    for (int st = kRedThreads / 2; st > 0; st >>= 1) {
-        if (tid < st) {
-#pragma unroll
-            for (int c = 0; c < 6; ++c) red[c][tid] += red[c][tid + st];
-        }
-        __syncthreads();
-    }
-    float tot[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) tot[c] = red[c][0];
-    __syncthreads();
+    block_reduce<kRedThreads, 6>(red, s, SumOp{});
     // ---- MR-STFT: per (item, resolution) sums over that pair's tiles
     if (tid < 4 * B) mr_item_stats(P, W, tid >> 2, tid & 3);
     __threadfence_block();
@@ -394,10 +355,10 @@ __global__ __launch_bounds__(kRedThreads) void crit_reduce_kernel(CritPlan P,
         for (int b = 0; b < B; ++b) esum_all += W.gtime[(int64_t)b * P.n];
         const float nbf = (float)B * (float)F;
         float l[8];
-        l[0] = (tot[0] / nbf + tot[1] / nbf) * P.w[0];
-        l[1] = (tot[2] / nbf) * P.w[1];
-        l[2] = (tot[3] / nbf + tot[4] / nbf) * P.w[2];
-        l[3] = (tot[5] / ((float)B * (float)n)) * P.w[3];
+        l[0] = (s[0] / nbf + s[1] / nbf) * P.w[0];
+        l[1] = (s[2] / nbf) * P.w[1];
+        l[2] = (s[3] / nbf + s[4] / nbf) * P.w[2];
+        l[3] = (s[5] / ((float)B * (float)n)) * P.w[3];
         l[4] = (esum_all / ((float)B * (float)M)) * P.w[4];
         float mr = 0.f;
         for (int q = 0; q < 4; ++q) mr += (qsum[q][0] + qsum[q][1]) + qsum[q][2];

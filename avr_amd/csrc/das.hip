@@ -20,6 +20,7 @@
 // (adjoint rfft).  Fixed summation orders throughout.
 #include <math.h>
 
+#include "block.h"
 #include "common.h"
 
 using namespace avr;
@@ -33,6 +34,7 @@ constexpr int kBins = kNfft / 2 + 1;
 constexpr int kFTile = 16;
 constexpr int kFTiles = (kBins + kFTile - 1) / kFTile;  // 17
 constexpr int kThreads = 256;
+constexpr int kStatThreads = 512;  // das_stats: one lane per direction, a power of two
 
 struct DasWs {
     float2* X;      // [2][8][257]
@@ -42,26 +44,16 @@ struct DasWs {
     int64_t bytes;
 };
 
-inline int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
-
 DasWs carve(void* base) {
     DasWs W{};
-    char* p = reinterpret_cast<char*>(base);
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) {
-        char* r = p ? p + o : nullptr;
-        o += align16(bytes);
-        return r;
-    };
-    W.X = reinterpret_cast<float2*>(take(2 * kMics * kBins * sizeof(float2)));
-    W.ppart = reinterpret_cast<float*>(take(2 * kFTiles * kDirs * 4));
-    W.power = reinterpret_cast<float*>(take(2 * kDirs * 4));
-    W.GX = reinterpret_cast<float2*>(take(kMics * kBins * sizeof(float2)));
-    W.bytes = o;
+    Arena A(base, 16);
+    W.X = A.take<float2>(2 * kMics * kBins);
+    W.ppart = A.take<float>(2 * kFTiles * kDirs);
+    W.power = A.take<float>(2 * kDirs);
+    W.GX = A.take<float2>(kMics * kBins);
+    W.bytes = A.bytes();
     return W;
 }
-
-__device__ __forceinline__ float sgnf(float x) { return (float)((x > 0.0f) - (x < 0.0f)); }
 
 // X[s][m][f] = sum_{t < min(n, 512)} time[m][t] e^{-2 pi i f t / 512}
 __global__ __launch_bounds__(kThreads) void das_spectrum_kernel(int n,
@@ -139,29 +131,6 @@ __global__ __launch_bounds__(kThreads) void das_power_kernel(const float2* __res
     }
 }
 
-__device__ __forceinline__ float block_max(float v, float* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int st = 256; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + st]);
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int st = 256; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
-
 struct DasStats {
     int target;           // argmax power_ori (first maximum)
     float lse_ce;         // logsumexp(power_pred)
@@ -169,8 +138,8 @@ struct DasStats {
     float a_p, a_o;       // softmax-weighted angles
 };
 
-// All 512 lanes: power = sum of tile partials, then the statistics of both
-// loss terms.  theta_k = deg2rad(k) from the host table `angles`.
+// All kStatThreads lanes: power = sum of tile partials, then the statistics of
+// both loss terms.  theta_k = deg2rad(k) from the host table `angles`.
 __device__ DasStats das_stats(const DasWs& W, const float* __restrict__ angles, float beta,
                               float* pw /*[2][360] LDS*/, float* red, int* redi) {
     for (int i = threadIdx.x; i < 2 * kDirs; i += blockDim.x) {
@@ -185,41 +154,34 @@ __device__ DasStats das_stats(const DasWs& W, const float* __restrict__ angles, 
     const bool live = k < kDirs;
     // argmax of power_ori, first index among equal maxima
     const float vo = live ? pw[kDirs + k] : -INFINITY;
-    const float mo = block_max(vo, red);
-    redi[threadIdx.x] = (live && vo == mo) ? k : kDirs;
-    __syncthreads();
-    for (int s2 = 256; s2 > 0; s2 >>= 1) {
-        if ((int)threadIdx.x < s2) redi[threadIdx.x] = min(redi[threadIdx.x], redi[threadIdx.x + s2]);
-        __syncthreads();
-    }
-    st.target = redi[0];
-    __syncthreads();
+    const float mo = block_max<kStatThreads>(vo, red);
+    st.target = block_min<kStatThreads>((live && vo == mo) ? k : kDirs, redi);
     // log-sum-exp of power_pred (cross entropy)
     const float vp = live ? pw[k] : -INFINITY;
-    const float mp = block_max(vp, red);
-    const float se = block_sum(live ? expf(vp - mp) : 0.f, red);
+    const float mp = block_max<kStatThreads>(vp, red);
+    const float se = block_sum<kStatThreads>(live ? expf(vp - mp) : 0.f, red);
     st.lse_ce = mp + logf(se);
     // softmax(beta * power) angle averages
     const float zp = live ? beta * pw[k] : -INFINITY;
     const float zo = live ? beta * pw[kDirs + k] : -INFINITY;
-    st.mx_p = block_max(zp, red);
-    const float mxo = block_max(zo, red);
+    st.mx_p = block_max<kStatThreads>(zp, red);
+    const float mxo = block_max<kStatThreads>(zo, red);
     const float ep = live ? expf(zp - st.mx_p) : 0.f;
     const float eo = live ? expf(zo - mxo) : 0.f;
-    st.sum_p = block_sum(ep, red);
-    const float so = block_sum(eo, red);
+    st.sum_p = block_sum<kStatThreads>(ep, red);
+    const float so = block_sum<kStatThreads>(eo, red);
     const float th = live ? angles[k] : 0.f;
-    st.a_p = block_sum(ep / st.sum_p * th, red);
-    st.a_o = block_sum(eo / so * th, red);
+    st.a_p = block_sum<kStatThreads>(ep / st.sum_p * th, red);
+    st.a_o = block_sum<kStatThreads>(eo / so * th, red);
     return st;
 }
 
-__global__ __launch_bounds__(512) void das_loss_kernel(const float* __restrict__ angles,
+__global__ __launch_bounds__(kStatThreads) void das_loss_kernel(const float* __restrict__ angles,
                                                        float beta, float w_reg, float w_ce,
                                                        DasWs W, float* __restrict__ losses) {
     __shared__ float pw[2 * kDirs];
-    __shared__ float red[512];
-    __shared__ int redi[512];
+    __shared__ float red[kStatThreads];
+    __shared__ int redi[kStatThreads];
     const DasStats st = das_stats(W, angles, beta, pw, red, redi);
     if (threadIdx.x < 2 * kDirs) W.power[threadIdx.x] = pw[threadIdx.x];
     if (threadIdx.x == 0) {
@@ -250,13 +212,13 @@ __device__ __forceinline__ float dpower(const DasStats& st, const float* pw, int
 }
 
 // dL/dX_pred[m][f] for the tile's frequencies (recomputes the beams).
-__global__ __launch_bounds__(512) void das_bwd_beam_kernel(const float2* __restrict__ steer,
+__global__ __launch_bounds__(kStatThreads) void das_bwd_beam_kernel(const float2* __restrict__ steer,
                                                            const float* __restrict__ angles,
                                                            float beta, float w_reg, float w_ce,
                                                            const float* __restrict__ g, DasWs W) {
     __shared__ float pw[2 * kDirs];
-    __shared__ float red[512];
-    __shared__ int redi[512];
+    __shared__ float red[kStatThreads];
+    __shared__ int redi[kStatThreads];
     __shared__ float gp[kDirs];
     __shared__ float2 xs[kMics][kFTile];
     __shared__ float2 beam[kDirs][kFTile];
@@ -373,7 +335,7 @@ extern "C" int avr_das_fwd(int32_t n, const float* pred_time, const float* ori_t
     if (int e = launch("das_power_kernel", das_power_kernel, dim3(kFTiles, 2), dim3(kThreads), 0, as_stream(stream),
                        reinterpret_cast<const float2*>(steer), W))
         return e;
-    return launch("das_loss_kernel", das_loss_kernel, dim3(1), dim3(512), 0, as_stream(stream), angles, beta, w_reg,
+    return launch("das_loss_kernel", das_loss_kernel, dim3(1), dim3(kStatThreads), 0, as_stream(stream), angles, beta, w_reg,
                   w_ce, W, losses);
 }
 
@@ -385,7 +347,7 @@ extern "C" int avr_das_bwd(int32_t n, const float* steer, const float* angles,
                 "avr_das_bwd: bad args");
     DasWs W = carve(ws);
     AVR_REQUIRE(ws_bytes >= W.bytes, "avr_das_bwd: workspace too small");
-    if (int e = launch("das_bwd_beam_kernel", das_bwd_beam_kernel, dim3(kFTiles), dim3(512), 0, as_stream(stream),
+    if (int e = launch("das_bwd_beam_kernel", das_bwd_beam_kernel, dim3(kFTiles), dim3(kStatThreads), 0, as_stream(stream),
                        reinterpret_cast<const float2*>(steer), angles, beta, w_reg, w_ce, grad_losses, W))
         return e;
     return launch("das_bwd_time_kernel", das_bwd_time_kernel, dim3(kMics), dim3(kThreads), 0, as_stream(stream),

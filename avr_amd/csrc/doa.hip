@@ -28,6 +28,7 @@
 //                        the valid frames of each group, fp64.
 #include <math.h>
 
+#include "block.h"
 #include "common.h"
 
 using namespace avr;
@@ -36,47 +37,6 @@ namespace {
 
 constexpr int kMics = 8;
 constexpr int kThreads = 256;
-
-inline int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
-
-// fixed-order block reductions over 256 threads (red: 256 entries of LDS)
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int st = kThreads / 2; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-        __syncthreads();
-    }
-    const T r = red[0];
-    __syncthreads();
-    return r;
-}
-template <typename T>
-__device__ __forceinline__ T block_max(T v, T* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int st = kThreads / 2; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + st]);
-        __syncthreads();
-    }
-    const T r = red[0];
-    __syncthreads();
-    return r;
-}
-// first index whose value equals the block's maximum (idx = the thread's
-// first best index, big where it has none)
-__device__ __forceinline__ int block_min_index(int idx, int* redi) {
-    redi[threadIdx.x] = idx;
-    __syncthreads();
-    for (int st = kThreads / 2; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) redi[threadIdx.x] = min(redi[threadIdx.x], redi[threadIdx.x + st]);
-        __syncthreads();
-    }
-    const int r = redi[0];
-    __syncthreads();
-    return r;
-}
 
 // Python's float % 360 (numpy's remainder): the sign of the divisor
 __device__ __forceinline__ double mod360(double a) {
@@ -103,12 +63,11 @@ struct DasDoaWs {
 
 DasDoaWs das_carve(void* base, int64_t G, int F, int K) {
     DasDoaWs W{};
-    char* p = reinterpret_cast<char*>(base);
+    Arena A(base, 16);
     const int tiles = (F + kDasFTile - 1) / kDasFTile;
-    const int64_t xb = align16(2 * G * kMics * F * (int64_t)sizeof(double2));
-    W.X = reinterpret_cast<double2*>(p);
-    W.ppart = reinterpret_cast<double*>(p ? p + xb : nullptr);
-    W.bytes = xb + align16(2 * G * tiles * K * (int64_t)sizeof(double));
+    W.X = A.take<double2>(2 * G * kMics * F);
+    W.ppart = A.take<double>(2 * G * tiles * K);
+    W.bytes = A.bytes();
     return W;
 }
 
@@ -209,21 +168,21 @@ __device__ DasDoaOut das_doa_stats(const double* __restrict__ ppart, int tiles, 
         pw[k] = p;
         lmax = fmax(lmax, p);
     }
-    const double mx = block_max(lmax, red);
+    const double mx = block_max<kThreads>(lmax, red);
     int first = 0x7fffffff;
     for (int k = threadIdx.x; k < K; k += kThreads)
         if (pw[k] == mx) {
             first = k;
             break;
         }
-    const int idx = block_min_index(first, redi);
+    const int idx = block_min<kThreads>(first, redi);
     double se = 0.0;
     for (int k = threadIdx.x; k < K; k += kThreads) se += exp(beta * pw[k] - beta * mx);
-    const double sum = block_sum(se, red);
+    const double sum = block_sum<kThreads>(se, red);
     double sa = 0.0;
     for (int k = threadIdx.x; k < K; k += kThreads)
         sa += exp(beta * pw[k] - beta * mx) / sum * (double)angles[k];
-    const double soft = block_sum(sa, red);
+    const double soft = block_sum<kThreads>(sa, red);
     DasDoaOut o;
     o.soft = mod360(soft);
     o.arg = mod360((double)angles[idx < K ? idx : 0]);
@@ -405,15 +364,15 @@ struct FrArgs {
 
 inline size_t frames_lds(int nfft) {
     size_t b = 0;
-    b += align16((int64_t)nfft * sizeof(float2));              // stw
-    b += align16((int64_t)kMics * nfft * sizeof(float));       // wy
-    b += kMics * kFrKC * sizeof(float2);                       // xs
-    b += 2 * align16((int64_t)kFrKC * kFrMat * sizeof(float2));  // A, V
-    b += kFrKC * 4 * sizeof(float4);                           // prm
-    b += kFrKC * kMics * sizeof(float2);                       // ev
-    b += kFrKC * sizeof(uint32_t);                             // dmin
-    b += align16(kFrDirs * sizeof(float));                     // P
-    b += kThreads * sizeof(float) + kThreads * sizeof(int);    // red, redi
+    b += align_up((int64_t)nfft * sizeof(float2), 16);              // stw
+    b += align_up((int64_t)kMics * nfft * sizeof(float), 16);       // wy
+    b += kMics * kFrKC * sizeof(float2);                            // xs
+    b += 2 * align_up((int64_t)kFrKC * kFrMat * sizeof(float2), 16);  // A, V
+    b += kFrKC * 4 * sizeof(float4);                                // prm
+    b += kFrKC * kMics * sizeof(float2);                            // ev
+    b += kFrKC * sizeof(uint32_t);                                  // dmin
+    b += align_up(kFrDirs * sizeof(float), 16);                     // P
+    b += kThreads * sizeof(float) + kThreads * sizeof(int);         // red, redi
     return b;
 }
 
@@ -722,14 +681,14 @@ __global__ __launch_bounds__(kThreads) void doa_frames_kernel(FrArgs a) {
         P[th] = v;
         bv = fmaxf(bv, v);
     }
-    const float mx = block_max(bv, red);
+    const float mx = block_max<kThreads>(bv, red);
     int first = 0x7fffffff;
     for (int th = tid; th < kFrDirs; th += kThreads)
         if (P[th] == mx) {
             first = th;
             break;
         }
-    const int idx = block_min_index(first, redi);
+    const int idx = block_min<kThreads>(first, redi);
     if (tid == 0) {
         a.est[fr] = idx < kFrDirs ? idx : 0;
         a.valid[fr] = 1;
@@ -789,7 +748,8 @@ __global__ __launch_bounds__(kThreads) void doa_frame_stats_kernel(
         s += v.y;
         cnt += 1.0;
     }
-    const double C = block_sum(c, red), S = block_sum(s, red), N = block_sum(cnt, red);
+    const double C = block_sum<kThreads>(c, red), S = block_sum<kThreads>(s, red);
+    const double N = block_sum<kThreads>(cnt, red);
     if (threadIdx.x == 0) {
         n_valid[g] = (int64_t)N;
         double mu = NAN, var = NAN, sd = NAN;

@@ -963,23 +963,22 @@ int bwd_layout(int64_t N, int L, const int64_t* off, const int32_t* res, BwdLayo
         return fail(AVR_E_ARG, "hashgrid: too many points for the partitioned backward");
     b.plan.nchunks = (int)std::max<int64_t>(nchunks, 1);
     b.total_parts = b.plan.pbase[L];
-    auto al = [](int64_t v) { return (v + 255) & ~(int64_t)255; };
-    int64_t o0 = 0;
-    b.counts = o0;
-    o0 += al((int64_t)b.total_parts * b.plan.nchunks * 4);
-    b.totals = o0;
-    o0 += al((int64_t)b.total_parts * 4);
-    b.part_start = o0;
-    o0 += al((int64_t)(b.total_parts + 1) * 4);
-    b.slice_base = o0;
-    o0 += al((int64_t)(b.total_parts + 1) * 4);
+    Arena A(nullptr, 256);  // offsets only: the launchers add them to the workspace pointer
+    b.counts = A.offset();
+    A.take<int32_t>((int64_t)b.total_parts * b.plan.nchunks);
+    b.totals = A.offset();
+    A.take<int32_t>(b.total_parts);
+    b.part_start = A.offset();
+    A.take<int32_t>(b.total_parts + 1);
+    b.slice_base = A.offset();
+    A.take<int32_t>(b.total_parts + 1);
     b.max_slices = b.total_parts + (int)(maxc / kDenseSlice) + 1;
     b.scatter_ok = b.plan.max_parts <= kMaxScatterParts;
-    b.glm = o0;  // the upstream gradient level-major (fp32 or fp16: sized for fp32)
-    o0 += al(N * L * 2 * 4);
-    b.contrib = o0;  // (key, v0, v1) per contribution
-    o0 += al(maxc * 12);
-    b.bytes = o0;
+    b.glm = A.offset();  // the upstream gradient level-major (fp32 or fp16: sized for fp32)
+    A.take<float>(N * L * 2);
+    b.contrib = A.offset();  // (key, v0, v1) per contribution
+    A.take<char>(maxc * 12);
+    b.bytes = A.bytes();
     // the workspace comes from the caller's allocator on every backward: past
     // this size the atomic kernel runs instead (no workspace, same += result)
     if (b.bytes > kMaxBwdWorkspaceBytes) b.scatter_ok = false;

@@ -27,6 +27,7 @@
 // tile's output leaves after those DMAs are issued, through a per-wave 4 KiB
 // LDS transpose as whole 128-byte lines: the stores are then younger than
 // the DMAs the next chunks wait for, so no wait covers them.
+#include "block.h"
 #include "common.h"
 
 #include <algorithm>
@@ -78,8 +79,6 @@ __device__ __forceinline__ f32x16 mma(frag8 a, frag8 b, f32x16 c) {
 __device__ __forceinline__ void ldma16(const void* g, uint32_t lds) {
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds), "v"(g) : "memory", "m0");
 }
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // s_waitcnt vmcnt(n) (gfx9 encoding) for the few counts the chunk loop uses
 #define AVR_L512_VMCNT(N) __builtin_amdgcn_s_waitcnt(((N) & 0xF) | (0x7 << 4) | (0xF << 8) | (((N) >> 4) << 14))

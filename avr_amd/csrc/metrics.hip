@@ -26,6 +26,7 @@
 // values do not depend on its batch.  All LDS is static, sized for n <= 12288.
 #include <math.h>
 
+#include "block.h"
 #include "common.h"
 
 using namespace avr;
@@ -48,8 +49,6 @@ struct MetWs {
     int64_t mr_bytes, bytes;
 };
 
-inline int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
-
 int check_shape(int B, int n) {
     AVR_REQUIRE(B >= 1 && B <= 256, "avr_metrics: 1 <= B <= 256 required");
     AVR_REQUIRE(n % 2 == 0, "avr_metrics: IR length n must be even");
@@ -60,38 +59,14 @@ int check_shape(int B, int n) {
 int carve(int B, int n, void* base, MetWs* W) {
     int64_t mr = 0;
     if (int e = mr3_workspace(B, n, &mr)) return e;
-    char* p = reinterpret_cast<char*>(base);
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) {
-        char* r = p ? p + o : nullptr;
-        o += align16(bytes);
-        return r;
-    };
+    Arena A(base, 16);
     const int64_t K = n / 2 + 1;
-    W->mr = take(mr);
+    W->mr = A.take<char>(mr);
     W->mr_bytes = mr;
-    W->X = reinterpret_cast<float2*>(take(2 * (int64_t)B * K * (int64_t)sizeof(float2)));
-    W->env = reinterpret_cast<float*>(take(2 * (int64_t)B * n * 4));
-    W->bytes = o;
+    W->X = A.take<float2>(2 * (int64_t)B * K);
+    W->env = A.take<float>(2 * (int64_t)B * n);
+    W->bytes = A.bytes();
     return 0;
-}
-
-template <int N>
-__device__ __forceinline__ void block_sum(float (*red)[kT], float* v) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < N; ++c) red[c][tid] = v[c];
-    __syncthreads();
-    for (int s = kT / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-#pragma unroll
-            for (int c = 0; c < N; ++c) red[c][tid] += red[c][tid + s];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int c = 0; c < N; ++c) v[c] = red[c][0];
 }
 
 // ------------------------------------------------------------ half spectrum
@@ -212,11 +187,15 @@ __global__ __launch_bounds__(kT) void met_hilbert_kernel(int B, int n, const flo
 struct EnergyLds {
     float S[kMaxN];      // x, then the cumulative sum, then the curve
     float seg[kT];
-    double red[4][kT];   // regression sums; argmin and C50 scratch before that
-    int sel[3];
+    double red[4][kT];   // regression sums; C50 and nearest-sample scratch before that
+};
+struct Nearest {  // distance to a target level and the sample it is at
+    float d;
+    int t;
 };
 static_assert(sizeof(EnergyLds) <= kLdsLimit, "met_energy_kernel: LDS over 64 KB");
-static_assert(sizeof(double) * 4 * kT >= sizeof(float) * 6 * kT, "argmin scratch fits the double rows");
+static_assert(sizeof(double) * 4 >= sizeof(Nearest) * 3 && sizeof(double) * 4 >= sizeof(float) * 2,
+              "the scratch fits the double rows");
 
 __global__ __launch_bounds__(kT) void met_energy_kernel(int B, int n, double fs, int s50,
                                                         const float* __restrict__ ori,
@@ -229,7 +208,6 @@ __global__ __launch_bounds__(kT) void met_energy_kernel(int B, int n, double fs,
     const int b = blockIdx.x, s = blockIdx.y;
     const float* x = (s ? pred : ori) + (int64_t)b * n;
     float* out = (s ? pred_energy : ori_energy) + (int64_t)b * n;
-    float(*redf)[kT] = reinterpret_cast<float(*)[kT]>(&L.red[0][0]);  // [<=8][kT] floats
     for (int i = tid; i < n; i += kT) L.S[i] = x[i];
     __syncthreads();
     const int seg_len = (n + kT - 1) / kT;
@@ -241,7 +219,7 @@ __global__ __launch_bounds__(kT) void met_energy_kernel(int B, int n, double fs,
         el[j >= s50] += sq;
     }
     L.seg[tid] = tot;
-    block_sum<2>(redf, el);  // early, late energy (syncs before and after)
+    block_reduce<kT, 2>(reinterpret_cast<float(*)[kT]>(L.red), el, SumOp{});  // early, late energy
     if (tid == 0) {
         float run = 0.f;
         for (int i = kT - 1; i >= 0; --i) {
@@ -261,8 +239,7 @@ __global__ __launch_bounds__(kT) void met_energy_kernel(int B, int n, double fs,
     const float e0 = 10.0f * log10f(L.S[0]);
     __syncthreads();
     const float target[3] = {-10.0f, -5.0f, -25.0f};
-    float bv[3] = {INFINITY, INFINITY, INFINITY};
-    int bi[3] = {n - 1, n - 1, n - 1};
+    Nearest best[3] = {{INFINITY, n - 1}, {INFINITY, n - 1}, {INFINITY, n - 1}};
     for (int t = tid; t < n; t += kT) {
         const float e = 10.0f * log10f(L.S[t]) - e0;
         L.S[t] = e;
@@ -270,37 +247,15 @@ __global__ __launch_bounds__(kT) void met_energy_kernel(int B, int n, double fs,
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float d = fabsf(e - target[c]);
-            if (d < bv[c]) {  // t ascends: the first minimum stays
-                bv[c] = d;
-                bi[c] = t;
-            }
+            if (d < best[c].d) best[c] = Nearest{d, t};  // t ascends: the first minimum stays
         }
     }
-    int(*redi)[kT] = reinterpret_cast<int(*)[kT]>(&redf[3][0]);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        redf[c][tid] = bv[c];
-        redi[c][tid] = bi[c];
-    }
-    __syncthreads();
-    for (int st = kT / 2; st > 0; st >>= 1) {
-        if (tid < st) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float v = redf[c][tid + st];
-                const int i = redi[c][tid + st];
-                if (v < redf[c][tid] || (v == redf[c][tid] && i < redi[c][tid])) {
-                    redf[c][tid] = v;
-                    redi[c][tid] = i;
-                }
-            }
-        }
-        __syncthreads();
-    }
-    if (tid < 3) L.sel[tid] = min(max(redi[tid][0], 0), n - 1);
-    __syncthreads();
-    const int i10 = L.sel[0], i5 = L.sel[1], i25 = L.sel[2];
-    __syncthreads();
+    // the smallest distance over the lanes, the earliest sample among equals
+    block_reduce<kT, 3>(reinterpret_cast<Nearest(*)[kT]>(L.red), best, [](Nearest a, Nearest b) {
+        return (b.d < a.d || (b.d == a.d && b.t < a.t)) ? b : a;
+    });
+    const int i10 = min(max(best[0].t, 0), n - 1), i5 = min(max(best[1].t, 0), n - 1),
+              i25 = min(max(best[2].t, 0), n - 1);
     // least squares of E[i5..i25] on u = t - i5 (stats.linregress on t / fs:
     // the slope per second is the slope per sample times fs)
     double a[4] = {0.0, 0.0, 0.0, 0.0};
@@ -311,21 +266,12 @@ __global__ __launch_bounds__(kT) void met_energy_kernel(int B, int n, double fs,
         a[2] += u * u;
         a[3] += u * y;
     }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) L.red[c][tid] = a[c];
-    __syncthreads();
-    for (int st = kT / 2; st > 0; st >>= 1) {
-        if (tid < st) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) L.red[c][tid] += L.red[c][tid + st];
-        }
-        __syncthreads();
-    }
+    block_reduce<kT, 4>(L.red, a, SumOp{});
     if (tid == 0) {
         float t60 = NAN;
         if (i25 > i5) {
             const double N = (double)(i25 - i5 + 1);
-            const double su = L.red[0][0], sy = L.red[1][0], suu = L.red[2][0], suy = L.red[3][0];
+            const double su = a[0], sy = a[1], suu = a[2], suy = a[3];
             const double slope = (N * suy - su * sy) / (N * suu - su * su) * fs;
             if (slope != 0.0) t60 = (float)(3.0 * (-20.0) / slope);
         }
@@ -384,16 +330,9 @@ __global__ __launch_bounds__(kT) void met_pair_kernel(int B, int n, int window,
     const float* ep = env + ((int64_t)B + b) * n;
     float mx = 0.f;
     for (int t = tid; t < n; t += kT) mx = fmaxf(mx, eo[t]);
-    __syncthreads();
-    L.red[0][tid] = mx;
-    __syncthreads();
-    for (int st = kT / 2; st > 0; st >>= 1) {
-        if (tid < st) L.red[0][tid] = fmaxf(L.red[0][tid], L.red[0][tid + st]);
-        __syncthreads();
-    }
-    mx = L.red[0][0];
+    mx = block_max<kT>(mx, L.red[0]);
     for (int t = tid; t < n; t += kT) acc[2] += fabsf(eo[t] - ep[t]) / mx;
-    block_sum<3>(L.red, acc);
+    block_reduce<kT, 3>(L.red, acc, SumOp{});
     if (tid < 3) rows[(int64_t)b * kCols + 6 + tid] = acc[tid];
 }
 

@@ -33,6 +33,7 @@
 // compiler-counted instruction.  One barrier per pair.  The pairs repeat with
 // period 16 over the items, so layer 2's last slice of an item runs in the
 // next item's first pair, followed by that item's output epilogue.
+#include "block.h"
 #include "common.h"
 
 #include <algorithm>
@@ -71,11 +72,6 @@ __device__ __forceinline__ void mlp_dma16(const void* sbase, uint32_t voff, uint
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds), "v"(voff), "s"(sbase)
                  : "memory", "m0");
 }
-
-// workgroup barrier that waits for the LDS traffic only: the W staging
-// loads and y stores in flight are not waited for (the compiler waits for a
-// load where its registers are used); "memory" keeps LDS accesses on their side
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));

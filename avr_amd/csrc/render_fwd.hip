@@ -1149,17 +1149,16 @@ CoreLayout core_layout(const avr_render_params* p, int B, int sig_dtype) {
     if (ks > nkc) ks = nkc;
     L.k_split = ks;
     L.P = (int32_t)(((S + 31) / 32) * ks);
-    auto al = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
-    int64_t o = 0;
-    L.w = o;
-    o += al((int64_t)B * R * S * 4);
-    L.delay = o;
-    o += al((int64_t)B * R * S * 4);
-    L.part = o;
-    o += al((int64_t)ns * B * S * T * 4);
-    L.spart = o;
-    o += al((int64_t)B * L.P * F * 8);
-    L.bytes = o;
+    Arena A(nullptr, 256);  // offsets only: the layout is exported to the caller
+    L.w = A.offset();
+    A.take<float>((int64_t)B * R * S);
+    L.delay = A.offset();
+    A.take<int32_t>((int64_t)B * R * S);
+    L.part = A.offset();
+    A.take<float>((int64_t)ns * B * S * T);
+    L.spart = A.offset();
+    A.take<float2>((int64_t)B * L.P * F);
+    L.bytes = A.bytes();
     return L;
 }
 }  // namespace

@@ -29,7 +29,8 @@ import ctypes
 import torch
 
 from . import _lib
-from .criterion import _ptr, _stream, _window_table
+from ._lib import _ptr, _stream
+from .criterion import _window_table
 from .renderer import _ir_twiddle
 
 METRIC_KEYS = ("Angle", "Amplitude", "Envelope", "T60", "C50", "EDT", "multi_stft")
