@@ -41,6 +41,7 @@
 // count, rays, cnt, weights, first delay) is loaded while the current item
 // computes, so an item's prologue is its rows' DMA and the first W tile.
 #include "common.h"
+#include "mma.h"
 #include "probe.h"
 #include "stationary.h"
 
@@ -52,69 +53,8 @@ AVR_PROBE_TU(avr_probe_set_exact)
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t frag8 __attribute__((ext_vector_type(4)));  // 8 packed 16-bit values
-
-template <typename E>
-__device__ __forceinline__ f32x16 mfma16(frag8 a, frag8 b, f32x16 c) {
-    if constexpr (std::is_same<E, __half>::value)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b),
-                                                      c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b),
-                                                       c, 0, 0, 0);
-}
-
-// x rounded to the 16-bit type E (round to nearest even) and back: the value
-// the unfused layer's 16-bit output holds
-template <typename E>
-__device__ __forceinline__ float round16(float x) {
-    if constexpr (std::is_same<E, __half>::value)
-        return __half2float(__float2half(x));
-    else
-        return __bfloat162float(__float2bfloat16(x));
-}
-
-// One 16-byte-per-lane LDS-DMA load: lane i's 16 bytes at g land at LDS byte
-// address lds + 16 i.  Issued as inline asm so the compiler does not treat
-// the in-flight DMA as an LDS write every later ds_read must wait for (with
-// the builtin it inserts vmcnt(0) inside the MFMA chain); completion is
-// waited for explicitly with counted vmcnt.
-__device__ __forceinline__ void dma_row16(const void* g, uint32_t lds) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds), "v"(g)
-                 : "memory", "m0");
-}
-
-// s_waitcnt vmcnt(n) (expcnt / lgkmcnt not waited on; gfx9 encoding)
-#define AVR_VMCNT(N) __builtin_amdgcn_s_waitcnt(((N) & 0xF) | (0x7 << 4) | (0xF << 8) | (((N) >> 4) << 14))
-
-// s_waitcnt vmcnt(n) for a run-time n (one case per value; above 31 the
-// wait is for 31, a longer wait than asked)
-__device__ __forceinline__ void wait_vm(int n) {
-    switch (n) {
-#define AVR_VMC(K) case K: AVR_VMCNT(K); break;
-        AVR_VMC(0) AVR_VMC(1) AVR_VMC(2) AVR_VMC(3) AVR_VMC(4) AVR_VMC(5) AVR_VMC(6) AVR_VMC(7)
-        AVR_VMC(8) AVR_VMC(9) AVR_VMC(10) AVR_VMC(11) AVR_VMC(12) AVR_VMC(13) AVR_VMC(14) AVR_VMC(15)
-        AVR_VMC(16) AVR_VMC(17) AVR_VMC(18) AVR_VMC(19) AVR_VMC(20) AVR_VMC(21) AVR_VMC(22) AVR_VMC(23)
-        AVR_VMC(24) AVR_VMC(25) AVR_VMC(26) AVR_VMC(27) AVR_VMC(28) AVR_VMC(29) AVR_VMC(30) AVR_VMC(31)
-#undef AVR_VMC
-        default: AVR_VMCNT(31); break;
-    }
-}
-
 // largest T of the 8-wave and the 4-wave items (exact_shape)
 constexpr int kExactMaxT[2] = {4096, 1024};
-
-// threadIdx.x through an empty asm: in a persistent kernel's item loop, the
-// per-lane values derived from it are formed where they are used instead of
-// hoisted out of the loop and held in registers (or spilled) across it
-__device__ __forceinline__ int opaque_tid() {
-    int t = threadIdx.x;
-    asm volatile("" : "+v"(t));
-    return t;
-}
 
 // bytes of one 32-t W tile in fragment order: KSM k-steps x 64 lanes x 16 B
 __host__ __device__ constexpr int xs_tile_bytes(int KSM) { return KSM * 1024; }
@@ -195,7 +135,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void head_exact_kernel(
         float wsv;
     };
     auto load_meta = [&](int item, Meta& m) {
-        const int tid = opaque_tid();
+        const int tid = opaque(threadIdx.x);
         m.item = item;
         const int it = min(item, nitems - 1);
         const int64_t col = (int64_t)it % ncol;
@@ -236,7 +176,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void head_exact_kernel(
     __syncthreads();
     for (int iter = 0; item < nitems; ++iter) {
         AVR_PROBE_DECL;
-        const int tid = opaque_tid();
+        const int tid = opaque(threadIdx.x);
         const int lane = tid & 63, half = lane >> 5, j = lane & 31;
         const int col = item % (int)ncol;  // items < 2^31 (checked by the host)
         const int blk = item / (int)ncol;
@@ -282,7 +222,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void head_exact_kernel(
                 stat_issue_round(reinterpret_cast<const uint16_t*>(hrow), ring + wave * 16384, 0);
                 stat_issue_round(reinterpret_cast<const uint16_t*>(hrow), ring + wave * 16384, 1);
                 AVR_PROBE_MARK(8);
-                stat_finish_rows512(reinterpret_cast<frag8_t(&)[32]>(a[0]), reinterpret_cast<const uint16_t*>(hrow),
+                stat_finish_rows512(a[0], reinterpret_cast<const uint16_t*>(hrow),
                                     ring + wave * 16384);
             } else {
 #pragma unroll
@@ -293,7 +233,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void head_exact_kernel(
                     if (ks >= ksn) a[0][ks] = frag8{0u, 0u, 0u, 0u};
 #pragma unroll
                 for (int ks = 0; ks < KSM; ++ks) asm volatile("" ::"v"(a[0][ks]));
-                AVR_VMCNT(0);
+                vmcnt<0>();
             }
             AVR_PROBE_MARK(9);
             // cnt, the item's weights and the waves' first live t into LDS
@@ -307,7 +247,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void head_exact_kernel(
             // staging area free (the ring may fill); cl, wl, dstart written.  A
             // bare barrier: nothing in flight on the vector-memory counter is
             // waited for (the claim's atomic)
-            __builtin_amdgcn_s_waitcnt(0xC07F);
+            lgkmcnt0();
             __builtin_amdgcn_s_barrier();
             AVR_PROBE_MARK(10);
             const int tb = dstart[0] / TT;       // first tile with a live ray of the item
@@ -318,14 +258,14 @@ __global__ __launch_bounds__(64 * WAVES, 2) void head_exact_kernel(
                 const char* src =
                     reinterpret_cast<const char*>(Wf) + (int64_t)tau * TILE + wave * DPW * 1024 + 16 * lane;
                 const uint32_t dst = ring_lds + slot * TILE + wave * DPW * 1024;
-                for (int d = 0; d < DPW; ++d) dma_row16(src + d * 1024, dst + d * 1024);
+                for (int d = 0; d < DPW; ++d) dma16(src + d * 1024, dst + d * 1024);
             };
             for (int i = 0; i < NB - 1; ++i)
                 if (tb + i < te) issue(tb + i, i);
             // the next item's metadata: in flight under this item, younger than
             // the first tiles, so only the tiles are waited for here
             load_meta(nxt, nx);
-            AVR_VMCNT(CLN + 3);  // the first tiles and the (older) claim have landed
+            vmcnt<CLN + 3>();  // the first tiles and the (older) claim have landed
             if (tid == 0) {
                 // published now, not at the item's end: no returning atomic is
                 // in flight at the loop's back edge (the compiler would wait for
@@ -334,7 +274,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void head_exact_kernel(
                 qnext[iter & 1] = item_of(3 * gq + claim);
                 published = true;
             }
-            __builtin_amdgcn_s_waitcnt(0xC07F);
+            lgkmcnt0();
             __builtin_amdgcn_s_barrier();
             AVR_PROBE_MARK(2);
 #ifdef AVR_PHASE_PROBES
@@ -383,7 +323,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void head_exact_kernel(
                     for (int q = 0; q < kHold; ++q)
                         if (ks >= q) keep_live(bw[(ks - q) % RS]);
                     if (ks + D < KSM) bw[(ks + D) % RS] = *reinterpret_cast<const frag8*>(bsrc + (ks + D) * 1024);
-                    if (ks % DSTEP == 0 && dma) dma_row16(dsrc + (ks / DSTEP) * 1024, ddst + (ks / DSTEP) * 1024);
+                    if (ks % DSTEP == 0 && dma) dma16(dsrc + (ks / DSTEP) * 1024, ddst + (ks / DSTEP) * 1024);
                 }
                 mfma_queue_wait();
 #pragma unroll
@@ -493,7 +433,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void head_exact_kernel(
                 }
                 AVR_PROBE_END(dma, 4);
                 AVR_PROBE_BEGIN(bar);
-                __builtin_amdgcn_s_waitcnt(0xC07F);  // every LDS access of tile tau (and the partials) done
+                lgkmcnt0();  // every LDS access of tile tau (and the partials) done
                 __builtin_amdgcn_s_barrier();
                 AVR_PROBE_END(bar, 5);
                 if (wave == summer(i)) sum_tile(tau, i % kPartBufs);
@@ -520,7 +460,6 @@ __global__ __launch_bounds__(64 * WAVES, 2) void head_exact_kernel(
 // W [T][K] -> Wf: for t-tile tau and k-step ks, the 64 lanes' 16-byte B
 // fragments of v_mfma_f32_32x32x16 (lane (j, half): W[32 tau + j][16 ks + 8 half
 // + 0..7]) contiguous, zero past T and K
-template <typename E>
 __global__ __launch_bounds__(256) void head_pack_exact_kernel(int T, int K, int KSM, const uint16_t* __restrict__ W,
                                                               frag8* __restrict__ Wf, int64_t n) {
     for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -612,7 +551,7 @@ extern "C" int avr_head_pack_w_exact(const avr_render_params* p, int32_t K, cons
     const int T = p->T, KSM = exact_ksm(K);
     const int64_t n = (int64_t)((T + 63) / 64) * 2 * KSM * 64;
     const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
-    return launch("avr_head_pack_w_exact", head_pack_exact_kernel<__half>, dim3(blocks), dim3(256), 0,
+    return launch("avr_head_pack_w_exact", head_pack_exact_kernel, dim3(blocks), dim3(256), 0,
                   as_stream(stream), T, (int)K, KSM, (const uint16_t*)W, (frag8*)Wf, n);
 }
 

@@ -29,6 +29,7 @@
 // the DMAs the next chunks wait for, so no wait covers them.
 #include "block.h"
 #include "common.h"
+#include "mma.h"
 
 #include <algorithm>
 
@@ -36,10 +37,6 @@ using namespace avr;
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t frag8 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kLK = 512;                  // K = N = 512
@@ -63,35 +60,17 @@ __host__ __device__ constexpr int lswz(int r, int p) {
     return kLPieces == 8 ? p ^ ((r >> 1) & 7) : p ^ ((r >> 2) & 3);
 }
 
-template <typename E>
-__device__ __forceinline__ f32x16 mma(frag8 a, frag8 b, f32x16 c) {
-    if constexpr (std::is_same<E, __half>::value)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b),
-                                                      c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b),
-                                                       c, 0, 0, 0);
-}
-
-// lane i's 16 bytes at g land at LDS byte lds + 16 i (issued as inline asm:
-// the compiler neither counts it nor treats it as an LDS write; completion is
-// waited for with explicit, counted vmcnt before the chunk's barrier)
-__device__ __forceinline__ void ldma16(const void* g, uint32_t lds) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds), "v"(g) : "memory", "m0");
-}
-
-// s_waitcnt vmcnt(n) (gfx9 encoding) for the few counts the chunk loop uses
-#define AVR_L512_VMCNT(N) __builtin_amdgcn_s_waitcnt(((N) & 0xF) | (0x7 << 4) | (0xF << 8) | (((N) >> 4) << 14))
+// s_waitcnt vmcnt(n) for the few counts the chunk loop uses
 __device__ __forceinline__ void wait_vm_l(int n) {
     switch (n) {
-        case 0: AVR_L512_VMCNT(0); break;
-        case 4: AVR_L512_VMCNT(4); break;
-        case 8: AVR_L512_VMCNT(8); break;
-        case 16: AVR_L512_VMCNT(16); break;
-        case 20: AVR_L512_VMCNT(20); break;
-        case 24: AVR_L512_VMCNT(24); break;
-        case 32: AVR_L512_VMCNT(32); break;
-        default: AVR_L512_VMCNT(0); break;  // (longer than needed, never shorter)
+        case 0: vmcnt<0>(); break;
+        case 4: vmcnt<4>(); break;
+        case 8: vmcnt<8>(); break;
+        case 16: vmcnt<16>(); break;
+        case 20: vmcnt<20>(); break;
+        case 24: vmcnt<24>(); break;
+        case 32: vmcnt<32>(); break;
+        default: vmcnt<0>(); break;  // (longer than needed, never shorter)
     }
 }
 
@@ -99,17 +78,6 @@ __device__ __forceinline__ void wait_vm_l(int n) {
 template <typename E>
 __device__ __forceinline__ uint32_t relu_pack(float a, float b) {
     return pack16<E>(__builtin_elementwise_maximum(a, 0.0f), __builtin_elementwise_maximum(b, 0.0f));
-}
-
-// v's 16-bit halves where m's are not <= 0 (threshold_backward's test,
-// `m <= 0 ? 0 : v`: +0, -0 and the negatives down to -inf zero it; positives,
-// +inf and every NaN keep v)
-template <typename E>
-__device__ __forceinline__ uint32_t keep_where_positive(uint32_t v, uint32_t m) {
-    constexpr uint32_t kInf = std::is_same<E, __half>::value ? 0x7c00u : 0x7f80u;
-    const uint32_t lo = m & 0xffffu, hi = m >> 16;
-    const bool zlo = lo == 0u || lo - 0x8000u <= kInf, zhi = hi == 0u || hi - 0x8000u <= kInf;
-    return (zlo ? 0u : (v & 0xffffu)) | (zhi ? 0u : (v & 0xffff0000u));
 }
 
 // kMask = false: y = relu(x W^T).  kMask = true: y = (x W^T) where
@@ -156,7 +124,7 @@ __global__ __launch_bounds__(512, 1) void linear512_relu_kernel(int64_t M, const
 #pragma unroll
         for (int i = 0; i < kW; ++i) {
             const int p = kW * wave + i;
-            ldma16(wsrc + p * 1024, base + kLXBytes + p * 1024);
+            dma16(wsrc + p * 1024, base + kLXBytes + p * 1024);
         }
 #pragma unroll
         for (int i = 0; i < kW; ++i) {
@@ -164,7 +132,7 @@ __global__ __launch_bounds__(512, 1) void linear512_relu_kernel(int64_t M, const
             const int r = kLRowsPerOp * q + lane / kLPieces;
             const int piece = lswz(r, lane % kLPieces);
             const int64_t row = std::min<int64_t>((int64_t)rt * kLTileRows + r, M - 1);
-            ldma16(x + row * kLK + kLKC * c + 8 * piece, base + q * 1024);
+            dma16(x + row * kLK + kLKC * c + 8 * piece, base + q * 1024);
         }
     };
 
@@ -218,7 +186,7 @@ __global__ __launch_bounds__(512, 1) void linear512_relu_kernel(int64_t M, const
 #pragma unroll
                 for (int a = 0; a < 2; ++a)
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) acc[a][q] = mma<E>(wfr[b][a], xfr[b][q], acc[a][q]);
+                    for (int q = 0; q < 4; ++q) acc[a][q] = mfma16<E>(wfr[b][a], xfr[b][q], acc[a][q]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {

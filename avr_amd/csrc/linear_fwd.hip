@@ -24,6 +24,7 @@
 // epilogue (ReLU, one rounding) leaves as 16-byte stores, 32 rows x 32 B per
 // wave-instruction.  No LDS round trip for the output.
 #include "common.h"
+#include "mma.h"
 #include "probe.h"
 #include "stationary.h"
 
@@ -35,45 +36,9 @@ AVR_PROBE_TU(avr_probe_set_linear)
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t frag8 __attribute__((ext_vector_type(4)));
-
 constexpr int kLK = 512;             // K
 constexpr int kLKS = kLK / 16;       // k-steps
 constexpr int kLTile = kLKS * 1024;  // one 32-column W tile in fragment order
-
-template <typename E>
-__device__ __forceinline__ f32x16 lmfma(frag8 a, frag8 b, f32x16 c) {
-    if constexpr (std::is_same<E, __half>::value)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b),
-                                                      c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b),
-                                                       c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void ldma16(const void* g, uint32_t lds) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds), "v"(g)
-                 : "memory", "m0");
-}
-
-#define AVR_LVMCNT(N) __builtin_amdgcn_s_waitcnt(((N) & 0xF) | (0x7 << 4) | (0xF << 8) | (((N) >> 4) << 14))
-
-// s_waitcnt vmcnt(n) for a run-time n (the immediate is a constant: one
-// case per value; n > 63 is clamped to 63, a shorter wait)
-__device__ __forceinline__ void wait_vm(int n) {
-    switch (n) {
-#define AVR_VMC(K) case K: AVR_LVMCNT(K); break;
-        AVR_VMC(0) AVR_VMC(1) AVR_VMC(2) AVR_VMC(3) AVR_VMC(4) AVR_VMC(5) AVR_VMC(6) AVR_VMC(7)
-        AVR_VMC(8) AVR_VMC(9) AVR_VMC(10) AVR_VMC(11) AVR_VMC(12) AVR_VMC(13) AVR_VMC(14) AVR_VMC(15)
-        AVR_VMC(16) AVR_VMC(17) AVR_VMC(18) AVR_VMC(19) AVR_VMC(20) AVR_VMC(21) AVR_VMC(22) AVR_VMC(23)
-        AVR_VMC(24) AVR_VMC(25) AVR_VMC(26) AVR_VMC(27) AVR_VMC(28) AVR_VMC(29) AVR_VMC(30) AVR_VMC(31)
-#undef AVR_VMC
-        default: AVR_LVMCNT(31); break;
-    }
-}
 
 // CT = 32 or 64 columns per W tile (64: half the barriers and DMA waits per
 // item, two accumulators per wave; the ring then holds 2 tiles of 64 KiB).
@@ -98,20 +63,20 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, 2
         const char* src = reinterpret_cast<const char*>(Wf) + (int64_t)tau * TILEB + wave * DPW * 1024 + 16 * lane;
         const uint32_t dst = ring_lds + slot * TILEB + wave * DPW * 1024;
 #pragma unroll
-        for (int d = 0; d < DPW; ++d) ldma16(src + d * 1024, dst + d * 1024);
+        for (int d = 0; d < DPW; ++d) dma16(src + d * 1024, dst + d * 1024);
     };
     // the wave's 32 rows (rows past M repeat the last one; their stores are
     // dropped), whole rows by LDS-DMA through the (still idle) ring
     frag8 a[kLKS];
     {
         const E* xr = x + min(r0 + 32 * wave + j, M - 1) * kLK;
-        stat_load_rows512(reinterpret_cast<frag8_t(&)[32]>(a), reinterpret_cast<const uint16_t*>(xr),
+        stat_load_rows512(a, reinterpret_cast<const uint16_t*>(xr),
                           lds_l + wave * 16384);
     }
     __syncthreads();  // every wave is done with the staging area: the ring may fill
     for (int i = 0; i < NB - 1; ++i)
         if (i < nt) issue(i, i);
-    AVR_LVMCNT(0);
+    vmcnt<0>();
     __syncthreads();
     AVR_PROBE_MARK(2);
     // the item's rows of y as a buffer resource: stores to rows past M fall
@@ -147,10 +112,10 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, 2
         for (int ks = 0; ks < kLKS; ++ks) {
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-                acc[c] = lmfma<E>(bw[ks % D][c], a[ks], acc[c]);
+                acc[c] = mfma16<E>(bw[ks % D][c], a[ks], acc[c]);
                 if (ks + D < kLKS) bw[ks % D][c] = *reinterpret_cast<const frag8*>(bsrc + c * kLTile + (ks + D) * 1024);
             }
-            if (ks % DSTEP == 0 && dnext) ldma16(dsrc + (ks / DSTEP) * 1024, ddst + (ks / DSTEP) * 1024);
+            if (ks % DSTEP == 0 && dnext) dma16(dsrc + (ks / DSTEP) * 1024, ddst + (ks / DSTEP) * 1024);
         }
         // epilogue: register r of acc[c] is column CT tau + 32 c + (r & 3) +
         // 8 (r >> 2) + 4 half of row rl.  Group pair (2p, 2p + 1) = columns
@@ -188,7 +153,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, 2
         }
         AVR_PROBE_END(dma, 4);
         AVR_PROBE_BEGIN(bar);
-        __builtin_amdgcn_s_waitcnt(0xC07F);  // every LDS read of tile tau done
+        lgkmcnt0();  // every LDS read of tile tau done
         __builtin_amdgcn_s_barrier();
         AVR_PROBE_END(bar, 5);
     }

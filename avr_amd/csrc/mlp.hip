@@ -23,6 +23,7 @@
 // slower, tools/bench_wgrad.py).  fp32 partials per n-range are summed in a
 // fixed order by a second kernel (deterministic).
 #include "common.h"
+#include "mma.h"
 
 #include <stdlib.h>
 
@@ -35,8 +36,6 @@ namespace {
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kTile = 128;   // dW tile edge (both m and k)
 constexpr int kSlab = 32;    // rows of n per LDS slab
@@ -58,23 +57,17 @@ __device__ __forceinline__ s16x4 tr_read(const char* lds_base, int byte_off) {
 // end read a zero row in device memory.
 __device__ __attribute__((aligned(16))) uint32_t g_wgrad_zero_row[64];  // 256 B of zeros (.bss)
 
-__device__ __forceinline__ void wg_dma16(const void* g, uint32_t lds) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds), "v"(g)
-                 : "memory", "m0");
-}
-
 // s_waitcnt vmcnt(4 ahead): this wave's DMAs of all but the `ahead` youngest
 // slabs landed (4 per slab; expcnt / lgkmcnt not waited on)
-#define AVR_WG_VMCNT(N) __builtin_amdgcn_s_waitcnt(((N) & 0xF) | (0x7 << 4) | (0xF << 8) | (((N) >> 4) << 14))
 __device__ __forceinline__ void wg_wait_slabs(int ahead) {
     switch (ahead) {
-        case 0: AVR_WG_VMCNT(0); break;
-        case 1: AVR_WG_VMCNT(4); break;
-        case 2: AVR_WG_VMCNT(8); break;
-        case 3: AVR_WG_VMCNT(12); break;
-        case 4: AVR_WG_VMCNT(16); break;
-        case 5: AVR_WG_VMCNT(20); break;
-        default: AVR_WG_VMCNT(24); break;
+        case 0: vmcnt<0>(); break;
+        case 1: vmcnt<4>(); break;
+        case 2: vmcnt<8>(); break;
+        case 3: vmcnt<12>(); break;
+        case 4: vmcnt<16>(); break;
+        case 5: vmcnt<20>(); break;
+        default: vmcnt<24>(); break;
     }
 }
 
@@ -132,8 +125,8 @@ __global__ __launch_bounds__(256) void linear_wgrad_dma_kernel(int64_t N, int M,
             const void* ga = ok ? (const void*)(gy + n * M + acol[u]) : (const void*)g_wgrad_zero_row;
             const void* gb = ok ? (const void*)(x + n * K + bcol[u]) : (const void*)g_wgrad_zero_row;
             const uint32_t off = (uint32_t)(1024 * (2 * wave + u));
-            wg_dma16(ga, __builtin_amdgcn_readfirstlane(slot + off));
-            wg_dma16(gb, __builtin_amdgcn_readfirstlane(slot + kImg + off));
+            dma16(ga, __builtin_amdgcn_readfirstlane(slot + off));
+            dma16(gb, __builtin_amdgcn_readfirstlane(slot + kImg + off));
         }
     };
 
@@ -328,27 +321,7 @@ __global__ __launch_bounds__(256) void linear_out1_bwd_kernel(int64_t N, int K, 
 // row's 4-column groups.  ACT: 0 none, 1 ReLU (the forward's epilogue),
 // 2 mask (0 where Mk <= 0, NaN keeps: a data gradient with the input ReLU's
 // backward, threshold_backward's selection).  One rounding of the fp32 sum.
-typedef uint32_t frag4u __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
-
-template <typename E>
-__device__ __forceinline__ f32x16 mfma16(frag4u a, frag4u b, f32x16 c) {
-    typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-    if constexpr (std::is_same<E, __half>::value)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c,
-                                                      0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b),
-                                                       c, 0, 0, 0);
-}
-
-template <typename E>
-__device__ __forceinline__ uint32_t narrow_keep(uint32_t v, uint32_t m) {
-    constexpr uint32_t kInf = std::is_same<E, __half>::value ? 0x7c00u : 0x7f80u;
-    const uint32_t lo = m & 0xffffu, hi = m >> 16;
-    const bool zlo = lo == 0u || lo - 0x8000u <= kInf, zhi = hi == 0u || hi - 0x8000u <= kInf;
-    return (zlo ? 0u : (v & 0xffffu)) | (zhi ? 0u : (v & 0xffff0000u));
-}
 
 constexpr int kNarrowRows = 128;  // rows per workgroup tile (4 waves x 32)
 #ifndef AVR_NARROW_STAGE
@@ -363,12 +336,12 @@ template <typename E, int NCT, int NKS, int ACT, bool STAGE>
 __global__ __launch_bounds__(256, 2) void narrow_mm_kernel(int64_t N, int R, int C, const E* __restrict__ X,
                                                          const E* __restrict__ Bt, const E* __restrict__ Mk,
                                                          E* __restrict__ Y) {
-    extern __shared__ frag4u bl[];  // [NCT * 32][R / 8 + 1] 16-byte pieces, then (STAGE) X [128][R / 8 + 1]
+    extern __shared__ frag8 bl[];  // [NCT * 32][R / 8 + 1] 16-byte pieces, then (STAGE) X [128][R / 8 + 1]
     const int pieces = R / 8, stride = pieces + 1;
-    frag4u* xs = bl + NCT * 32 * stride;
+    frag8* xs = bl + NCT * 32 * stride;
     for (int i = threadIdx.x; i < NCT * 32 * pieces; i += 256) {
         const int c = i / pieces, p = i % pieces;
-        bl[c * stride + p] = c < C ? *reinterpret_cast<const frag4u*>(Bt + (int64_t)c * R + 8 * p) : frag4u{};
+        bl[c * stride + p] = c < C ? *reinterpret_cast<const frag8*>(Bt + (int64_t)c * R + 8 * p) : frag8{};
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
@@ -376,15 +349,15 @@ __global__ __launch_bounds__(256, 2) void narrow_mm_kernel(int64_t N, int R, int
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t n = tile * kNarrowRows + 32 * wave + j;
         const bool ok = n < N;
-        frag4u xf[NKS];
+        frag8 xf[NKS];
         if constexpr (STAGE) {
             constexpr int kP = 2 * NKS;  // pieces per row
-            frag4u v[NKS];               // 128 kP pieces over 256 threads: kP / 2 each
+            frag8 v[NKS];               // 128 kP pieces over 256 threads: kP / 2 each
 #pragma unroll
             for (int i = 0; i < NKS; ++i) {
                 const int idx = threadIdx.x + 256 * i, row = idx / kP, p = idx % kP;
                 const int64_t nn = tile * kNarrowRows + row;
-                v[i] = nn < N ? *reinterpret_cast<const frag4u*>(X + nn * R + 8 * p) : frag4u{};
+                v[i] = nn < N ? *reinterpret_cast<const frag8*>(X + nn * R + 8 * p) : frag8{};
             }
             __syncthreads();  // the previous tile's fragment reads are done
 #pragma unroll
@@ -398,14 +371,14 @@ __global__ __launch_bounds__(256, 2) void narrow_mm_kernel(int64_t N, int R, int
         } else {
             const E* xr = X + (ok ? n : 0) * R + 8 * h;
 #pragma unroll
-            for (int s = 0; s < NKS; ++s) xf[s] = ok ? *reinterpret_cast<const frag4u*>(xr + 16 * s) : frag4u{};
+            for (int s = 0; s < NKS; ++s) xf[s] = ok ? *reinterpret_cast<const frag8*>(xr + 16 * s) : frag8{};
         }
         f32x16 acc[NCT];
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) acc[ct] = f32x16{};
         // Bt fragments one k-step ahead of the MFMAs that use them (the
         // fences keep hipcc from hoisting every k-step's reads at once)
-        frag4u af[2][NCT];
+        frag8 af[2][NCT];
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) af[0][ct] = bl[(32 * ct + j) * stride + h];
 #pragma unroll
@@ -437,8 +410,8 @@ __global__ __launch_bounds__(256, 2) void narrow_mm_kernel(int64_t N, int R, int
                 u32x2v o = {pack16<E>(a0, a1), pack16<E>(a2, a3)};
                 if (ACT == 2) {
                     const u32x2v m = *reinterpret_cast<const u32x2v*>(Mk + n * C + c0);
-                    o[0] = narrow_keep<E>(o[0], m[0]);
-                    o[1] = narrow_keep<E>(o[1], m[1]);
+                    o[0] = keep_where_positive<E>(o[0], m[0]);
+                    o[1] = keep_where_positive<E>(o[1], m[1]);
                 }
                 *reinterpret_cast<u32x2v*>(Y + n * C + c0) = o;
             }

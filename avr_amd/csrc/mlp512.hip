@@ -35,6 +35,7 @@
 // next item's first pair, followed by that item's output epilogue.
 #include "block.h"
 #include "common.h"
+#include "mma.h"
 
 #include <algorithm>
 
@@ -63,37 +64,12 @@ namespace {
 #define AVR_MLP_TSTORE 0
 #endif
 
-// s_waitcnt vmcnt(n) (gfx9 encoding; expcnt / lgkmcnt not waited on)
-#define AVR_MLP_VMCNT(N) __builtin_amdgcn_s_waitcnt(((N) & 0xF) | (0x7 << 4) | (0xF << 8) | (((N) >> 4) << 14))
-
-// lane i's 16 bytes at sbase + voff land at LDS byte lds + 16 i (scalar base,
-// 32-bit lane offset: one VGPR for every piece)
-__device__ __forceinline__ void mlp_dma16(const void* sbase, uint32_t voff, uint32_t lds) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds), "v"(voff), "s"(sbase)
-                 : "memory", "m0");
-}
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t frag8 __attribute__((ext_vector_type(4)));
-
 constexpr int kMK = 512;                  // width (K and N of both layers)
 constexpr int kMKS = kMK / 16;            // k-steps (32)
 constexpr int kMN = kMK / 32;             // 32-column output tiles per layer (16)
 constexpr int kMPair = 2 * kMKS * 1024;   // bytes of one pair: 32 + 32 pieces of 1 KiB
 constexpr int kMRows = 128;               // rows per work item (4 waves x 32)
 constexpr int kMShare = 2 * kMKS / 4;     // 1 KiB pieces of a pair per wave (16)
-
-template <typename E>
-__device__ __forceinline__ f32x16 mma(frag8 a, frag8 b, f32x16 c) {
-    if constexpr (std::is_same<E, __half>::value)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b),
-                                                      c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b),
-                                                       c, 0, 0, 0);
-}
 
 // acc = C^T of a 32x32 tile (lane (j, half), register r: row j, column
 // (r & 3) + 8 (r >> 2) + 4 half), rectified and rounded to E: the fragments
@@ -139,7 +115,7 @@ __global__ __launch_bounds__(256, 1) void mlp512x2_kernel(int64_t M, const E* __
         const char* src = reinterpret_cast<const char*>(Wf) + (int64_t)p * kMPair + kMShare * wave * 1024;
         const uint32_t dst = (uint32_t)(uintptr_t)(lds_m + slot * kMPair) + kMShare * wave * 1024;
 #pragma unroll
-        for (int i = 0; i < kMShare; ++i) mlp_dma16(src + i * 1024, 16 * lane, dst + i * 1024);
+        for (int i = 0; i < kMShare; ++i) dma16_sbase(src + i * 1024, 16 * lane, dst + i * 1024);
     };
     auto write_half = [&](int slot, int h) {
         frag8* dst = reinterpret_cast<frag8*>(lds_m + slot * kMPair) + (kMShare * wave + 8 * h) * 64 + lane;
@@ -216,10 +192,10 @@ __global__ __launch_bounds__(256, 1) void mlp512x2_kernel(int64_t M, const E* __
 #pragma unroll
         for (int st = 0; st < 4 * kMKS / 2; ++st) {
             if ((st & 1) == 0) {
-                if (t1) acc1 = mma<E>(bw[st % D], ax[st >> 1], acc1);
+                if (t1) acc1 = mfma16<E>(bw[st % D], ax[st >> 1], acc1);
             } else {
                 const int i = st >> 1;
-                acc2[i >> 1] = mma<E>(bw[st % D], bx[i & 1], acc2[i >> 1]);
+                acc2[i >> 1] = mfma16<E>(bw[st % D], bx[i & 1], acc2[i >> 1]);
             }
             if (st + D < 2 * kMKS) bw[st % D] = ring[piece(st + D) * 64];
 #if AVR_MLP_SCHED
@@ -236,7 +212,7 @@ __global__ __launch_bounds__(256, 1) void mlp512x2_kernel(int64_t M, const E* __
     load_rows(blockIdx.x);
     if constexpr (AVR_MLP_DMA) {
         dma_pair(0, 0);
-        AVR_MLP_VMCNT(0);
+        vmcnt<0>();
     } else {
         load_half(0, 0);
         write_half(0, 0);
@@ -263,7 +239,7 @@ __global__ __launch_bounds__(256, 1) void mlp512x2_kernel(int64_t M, const E* __
                 // (the previous pair's pieces were waited for; the rows and y
                 // stores here): the compiler, which cannot count the DMA
                 // below, then waits for nothing inside the pair
-                AVR_MLP_VMCNT(0);
+                vmcnt<0>();
                 if (!(AVR_MLP_DBG & 1)) dma_pair((c + 1) % kMN, slot1);
             } else if (!(AVR_MLP_DBG & 1)) {
                 write_half(slot1, 0);
@@ -305,10 +281,10 @@ __global__ __launch_bounds__(256, 1) void mlp512x2_kernel(int64_t M, const E* __
                 // stores of pair 0 and the next item's row loads of pair 15
                 const int young = (c == 0 && prev >= 0 && !(AVR_MLP_DBG & 4) ? 2 * kMN : 0) +
                                   (c == kMN - 1 && it + G < nitems ? kMKS : 0);
-                if (young == 0) AVR_MLP_VMCNT(0);
-                else if (young == 2 * kMN) AVR_MLP_VMCNT(2 * kMN);
-                else if (young == kMKS) AVR_MLP_VMCNT(kMKS);
-                else AVR_MLP_VMCNT(2 * kMN + kMKS);
+                if (young == 0) vmcnt<0>();
+                else if (young == 2 * kMN) vmcnt<2 * kMN>();
+                else if (young == kMKS) vmcnt<kMKS>();
+                else vmcnt<2 * kMN + kMKS>();
             }
             if (!(AVR_MLP_DBG & 2)) lds_barrier();
         }

@@ -38,33 +38,18 @@
 // carried as raw dwords; E only decides the conversions and the MFMA
 // (v_mfma_f32_32x32x16_bf16 / _f16).
 #include "common.h"
+#include "mma.h"
 #include "probe.h"
 
 using namespace avr;
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef u32x4v frag8;  // 8 packed 16-bit values (one MFMA operand per lane)
-
-// the 16-bit MLP element types: bf16 (__bf16) or fp16 (_Float16)
-template <typename E>
-__device__ __forceinline__ f32x16 mfma16(frag8 a, frag8 b, f32x16 c) {
-    if constexpr (std::is_same<E, _Float16>::value)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b),
-                                                      c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b),
-                                                       c, 0, 0, 0);
-}
 
 constexpr int kChunk = 32768;  // bytes of packed fragments per LDS stage
 constexpr int kFrag = 1024;    // one fragment: 64 lanes x 8 bf16
@@ -101,9 +86,7 @@ __device__ __forceinline__ uint32_t pack2(float a, float b) {
     else
         return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2v){a, b}, bf16x2));
 }
-// fp32 -> E -> fp32 (the 16-bit rounding of one value) and its bits
-template <typename E>
-__device__ __forceinline__ float round16(float v) { return (float)(E)v; }
+// the bits of v rounded to E
 template <typename E>
 __device__ __forceinline__ uint16_t bits16(float v) { return __builtin_bit_cast(uint16_t, (E)v); }
 
@@ -142,7 +125,7 @@ __device__ __forceinline__ frag8 load8(const Src& s, int64_t row, int width, int
             }
         }
     } else if (s.dtype == AVR_DTYPE_F16) {
-        const u32x4v v = *reinterpret_cast<const u32x4v*>(
+        const frag8 v = *reinterpret_cast<const frag8*>(
             static_cast<const __half*>(s.p) + row * width + col);
         Vec16<__half>::cvt(v, f);
     } else {
@@ -181,8 +164,8 @@ template <int WAVES, int DBG = 0>
 struct Stager {
     static constexpr bool kDma = (DBG & 32) != 0;
     static constexpr int kPer = kChunk / (64 * WAVES * 16);
-    u32x4v r[kDma ? 1 : kPer];
-    const u32x4v* src;
+    frag8 r[kDma ? 1 : kPer];
+    const frag8* src;
     char* lds;
     int cur, n_chunks, tid;
     bool defer = false;  // DMA mode: finish_chunk leaves the next issue to issue_deferred()
@@ -192,14 +175,13 @@ struct Stager {
         pending = -1;
     }
     __device__ void issue(int c) {
-        const u32x4v* p = src + (int64_t)c * (kChunk / 16);
+        const frag8* p = src + (int64_t)c * (kChunk / 16);
         if constexpr (kDma) {
             const uint32_t base = (uint32_t)(uintptr_t)(lds + (c & 1) * kChunk) + (tid & ~63) * 16;
 #pragma unroll
             for (int i = 0; i < kPer; ++i) {
                 const uint32_t m = __builtin_amdgcn_readfirstlane(base + 64 * WAVES * 16 * i);
-                asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
-                             ::"s"(m), "v"(p + tid + 64 * WAVES * i) : "memory", "m0");
+                dma16(p + tid + 64 * WAVES * i, m);
             }
         } else {
 #pragma unroll
@@ -208,7 +190,7 @@ struct Stager {
     }
     __device__ void write(int c) {
         if constexpr (!kDma) {
-            u32x4v* d = reinterpret_cast<u32x4v*>(lds + (c & 1) * kChunk);
+            frag8* d = reinterpret_cast<frag8*>(lds + (c & 1) * kChunk);
 #pragma unroll
             for (int i = 0; i < kPer; ++i) d[tid + 64 * WAVES * i] = r[i];
         }
@@ -220,7 +202,7 @@ struct Stager {
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
     __device__ void start(const char* wpack, char* lds_base, int chunks) {
-        src = reinterpret_cast<const u32x4v*>(wpack);
+        src = reinterpret_cast<const frag8*>(wpack);
         lds = lds_base;
         tid = threadIdx.x;
         n_chunks = chunks;
@@ -540,11 +522,11 @@ __device__ __forceinline__ void store_h1(const Args& a, const f32x16 (&acc)[NT][
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int row = 8 * q + (lane >> 3), chunk = lane & 7;
-                const u32x4v v = *reinterpret_cast<const u32x4v*>(tr + row * 128 + ((chunk ^ (row & 7)) * 16));
+                const frag8 v = *reinterpret_cast<const frag8*>(tr + row * 128 + ((chunk ^ (row & 7)) * 16));
                 const int64_t nr = n0 + 32 * nt + row;
                 // (STORE = false: timing experiments; a.ldb < 0 never holds)
                 if (STORE ? nr < a.N : a.ldb < 0) {
-                    u32x4v* dst = reinterpret_cast<u32x4v*>(a.base + nr * a.ldb + 128 * c + 64 * p + 8 * chunk);
+                    frag8* dst = reinterpret_cast<frag8*>(a.base + nr * a.ldb + 128 * c + 64 * p + 8 * chunk);
                     if (a.nt_store)
                         __builtin_nontemporal_store(v, dst);
                     else
