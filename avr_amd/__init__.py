@@ -7,6 +7,7 @@ hand-written HIP kernels for gfx950 behind the C-ABI in `include/avr_hip.h`.
 from .renderer import (  # noqa: F401
     AVRRender,
     RenderCore,
+    RenderCoreMC,
     denormalize_points,
     normalize_points,
     ray_directions,
@@ -38,6 +39,7 @@ from .doa import (  # noqa: F401
     frame_stats,
 )
 from .options import KernelOptions  # noqa: F401
+from . import spatial  # noqa: F401
 from . import workloads  # noqa: F401
 
 __version__ = "0.1.0"

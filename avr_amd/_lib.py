@@ -117,6 +117,11 @@ _SIGS = {
     "avr_sample_rays_dev": (ctypes.c_int, [_vp, _c_i32, _vp, _c_i32] + [_vp] * 9),
     "avr_sample_rays_staged": (ctypes.c_int, [_vp, _c_i32, _vp, _c_i32, _c_i32] + [_vp] * 7),
     "avr_reduce_splits": (ctypes.c_int, [_vp, _c_i32, _c_i32, _vp]),
+    "avr_ray_reduce_mc_fwd": (ctypes.c_int, [_vp, _c_i32, _c_i32, _vp, _c_i32, _vp, _vp, _vp, _c_i64, _c_i32,
+                                             _vp, _vp]),
+    "avr_reduce_mc_splits": (ctypes.c_int, [_vp, _c_i32, _c_i32, _c_i32, _vp, _vp]),
+    "avr_ray_reduce_mc_bwd": (ctypes.c_int, [_vp, _c_i32, _c_i32, _vp, _c_i32, _vp, _vp, _vp, _vp, _c_i64,
+                                             _vp, _vp, _vp]),
     "avr_dft_phase_fwd": (ctypes.c_int, [_vp, _c_i32, _vp, _c_i32, _vp, _vp, _vp, _vp, _c_i32, _vp, _vp]),
     "avr_spectrum_finalize": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, _vp, _vp, _vp]),
     "avr_irfft": (ctypes.c_int, [_c_i32, _c_i32, _vp, _vp, _vp, _vp]),

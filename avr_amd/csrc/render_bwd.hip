@@ -293,6 +293,162 @@ __global__ __launch_bounds__(MAXT) void ray_reduce_bwd_kernel(
     }
 }
 
+// ------------------------------- ray reduce backward, CB receiver channels
+// Adjoint of ray_reduce_mc_fwd_kernel for channels c0..c0+CB-1 of every pose:
+// with q[r,t] = sum_j g[b,c0+j,r] * gz[b*C+c0+j,s,t] (j ascending),
+//   grad_x = w*[live]*q ,  grad_w = sum_t [live]*x*q
+// ray_reduce_bwd_kernel's twin with one column per group: a lane keeps the
+// CB channels' gz slots in registers, so the signal is read once per block
+// of channels.  ACCUM: a later block of the same call adds into grad_x and
+// grad_w (grad_x is then rounded to the signal type once more).
+// LDS: w_l[nr], d_l[nr], dot_l[nr], g_l[CB][nr].
+template <typename Tin, bool VECTOR, int CPT, int CB, int MAXT, bool ACCUM>
+__global__ __launch_bounds__(MAXT) void ray_reduce_mc_bwd_kernel(
+    avr_render_params pp, const Tin* __restrict__ sig, const float* __restrict__ gz, const float* __restrict__ w,
+    const int32_t* __restrict__ delay, const float* __restrict__ gain, int64_t gain_b_stride, int C, int c0,
+    Tin* gsig, float* gw, int B, int R, int S, int T, int rays_per_split, int64_t total) {
+    constexpr int VEC = VECTOR ? Vec16<Tin>::N : 1;
+    extern __shared__ float lds_mcb[];
+    const int nthreads = blockDim.x, lane = threadIdx.x & 63;
+    const int split = blockIdx.x, s = blockIdx.y, b = blockIdx.z;
+    const int r0 = split * rays_per_split;
+    const int nr = max(0, min(R, r0 + rays_per_split) - r0);
+    const int ld = max(nr, 1);
+    float* w_l = lds_mcb;
+    int* d_l = reinterpret_cast<int*>(lds_mcb + ld);
+    float* dot_l = lds_mcb + 2 * ld;
+    float* g_l = lds_mcb + 3 * ld;
+    const float* gb = gain + (int64_t)b * gain_b_stride + (int64_t)c0 * R + r0;
+    for (int i = threadIdx.x; i < nr; i += nthreads) {
+        const int64_t idx = ((int64_t)b * R + r0 + i) * S + s;
+        w_l[i] = w[idx];
+        d_l[i] = delay[idx];
+        dot_l[i] = ACCUM ? gw[idx] : 0.0f;
+#pragma unroll
+        for (int j = 0; j < CB; ++j) g_l[j * ld + i] = gb[(int64_t)j * R + i];
+    }
+    const int64_t row0 = (((int64_t)b * R + r0) * S + s) * (int64_t)T;
+    const int phase = (int)(row0 % VEC);
+    const int nchunks = (T + phase + VEC - 1) / VEC;
+    const int64_t row_stride = (int64_t)S * T;
+    const int lim = tail_limit(pp, s);
+
+    float gv[CB][CPT][VEC];
+    int tk[CPT][VEC];  // t of each slot (-1: outside the row)
+    int tm[CPT][VEC];  // t if inside the tail window t < T-1-shift[s], else -1
+    int tmax[CPT];     // per chunk: largest tm (-1: no live slot)
+    bool full[CPT];    // chunk lies inside the row: vector store allowed
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) {
+        const int j = threadIdx.x + c * nthreads;
+        const int ebase = j * VEC - phase;
+        full[c] = j < nchunks && ebase >= 0 && ebase + VEC <= T;
+        tmax[c] = -1;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            const int e = ebase + k;
+            const bool ok = j < nchunks && e >= 0 && e < T;
+            tk[c][k] = ok ? e : -1;
+#pragma unroll
+            for (int q = 0; q < CB; ++q)
+                gv[q][c][k] = ok ? gz[(((int64_t)b * C + c0 + q) * S + s) * (int64_t)T + e] : 0.0f;
+            tm[c][k] = (ok && e < lim) ? e : -1;
+            tmax[c] = max(tmax[c], tm[c][k]);
+        }
+    }
+    __syncthreads();
+
+    auto load_chunk = [&](int64_t rowbase, int c, bool need, float* x) {
+        const int j = threadIdx.x + c * nthreads;
+        if constexpr (VECTOR) {
+            load16_masked(sig + rowbase, (uint32_t)nchunks * 16u,
+                          need ? (uint32_t)j * 16u : kSkip, x);
+        } else {
+            const int64_t e0 = rowbase + j;
+            x[0] = (need && j < nchunks && e0 < total) ? load_f(sig, e0) : 0.0f;
+        }
+    };
+    auto finish = [&](int r, int64_t rowbase, float (*x)[VEC]) {
+        const float ws = w_l[r];
+        const int ds = d_l[r];
+        float g[CB];
+#pragma unroll
+        for (int q = 0; q < CB; ++q) g[q] = g_l[q * ld + r];
+        float dot = 0.0f;
+#pragma unroll
+        for (int c = 0; c < CPT; ++c) {
+            const int j = threadIdx.x + c * nthreads;
+            const int64_t e0 = rowbase + (int64_t)j * VEC;
+            const bool vec_store = VECTOR && full[c];
+            float o[VEC];
+            if constexpr (ACCUM) {
+                if (vec_store) {
+                    if constexpr (VECTOR)
+                        Vec16<Tin>::cvt(*reinterpret_cast<const typename Vec16<Tin>::raw*>(gsig + e0), o);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) o[k] = tk[c][k] >= 0 ? load_f(gsig, e0 + k) : 0.0f;
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) o[k] = 0.0f;
+            }
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                float qs = g[0] * gv[0][c][k];
+#pragma unroll
+                for (int q = 1; q < CB; ++q) qs = fmaf(g[q], gv[q][c][k], qs);
+                const float gm = (tm[c][k] >= ds) ? qs : 0.0f;
+                o[k] = ACCUM ? fmaf(ws, gm, o[k]) : ws * gm;
+                dot = fmaf(gm, x[c][k], dot);
+            }
+            if (vec_store) {
+                if constexpr (VECTOR) {
+                    if constexpr (ACCUM)
+                        store16(gsig + e0, o);
+                    else
+                        store16_nt(gsig + e0, o);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < VEC; ++k)
+                    if (tk[c][k] >= 0) store_f(gsig, e0 + k, o[k]);
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) dot += __shfl_xor(dot, off, 64);
+        if (lane == 0) atomicAdd(&dot_l[r], dot);
+    };
+
+    constexpr int U = 4;  // rays in flight per lane
+    int r = 0;
+    for (; r + U <= nr; r += U) {
+        float x[U][CPT][VEC];
+        bool need[U][CPT];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int c = 0; c < CPT; ++c) need[u][c] = tmax[c] >= d_l[r + u];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t bu = row0 + (int64_t)(r + u) * row_stride - phase;
+#pragma unroll
+            for (int c = 0; c < CPT; ++c) load_chunk(bu, c, need[u][c], x[u][c]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) finish(r + u, row0 + (int64_t)(r + u) * row_stride - phase, x[u]);
+    }
+    for (; r < nr; ++r) {
+        float xa[CPT][VEC];
+        const int64_t ba = row0 + (int64_t)r * row_stride - phase;
+#pragma unroll
+        for (int c = 0; c < CPT; ++c) load_chunk(ba, c, tmax[c] >= d_l[r], xa[c]);
+        finish(r, ba, xa);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nr; i += nthreads) gw[((int64_t)b * R + r0 + i) * S + s] = dot_l[i];
+}
+
 // --------------------------------------------------- weights backward
 // Per ray (one wavefront), with f_k = (1-alpha_k)+1e-6, T_s = prod_{k<s} f_k:
 //   dL/dalpha_s = T_s * (gw_s - U_s),  U_s = sum_{j>s} gw_j alpha_j prod_{s<k<j} f_k
@@ -467,6 +623,113 @@ extern "C" int avr_ray_reduce_bwd(const avr_render_params* p, int32_t B, const v
         sig_dtype, "avr_ray_reduce_bwd", [&](auto tag) {
             return launch_rb_any<typename decltype(tag)::type>(p, B, signal, gz, w, delay, grad_signal, grad_w,
                                                               as_stream(stream));
+        });
+}
+
+namespace {
+constexpr int mc_block(int left) { return left >= 4 ? 4 : left >= 2 ? 2 : 1; }
+
+struct McBwdShape {
+    int cpt, threads, rps;
+};
+
+// Chunks per lane, block size and rays per split (a split's slab of
+// (12 + 4*CB) bytes per ray within the 64 KiB a launch gets unasked) of the
+// multi-channel backward; one sample per column group.
+template <int VEC>
+int mc_bwd_shape(const avr_render_params* p, int B, int cb, McBwdShape* sh) {
+    const int R = n_rays(*p), S = p->n_samples, T = p->T;
+    int max_phase = 0;
+    for (int s0 = 0; s0 < S && s0 < VEC; ++s0) max_phase = max(max_phase, (int)(((int64_t)s0 * T) % VEC));
+    const int nch = (T + max_phase + VEC - 1) / VEC;
+    sh->cpt = 1;
+    while ((nch + sh->cpt - 1) / sh->cpt > kMaxRbThreads) ++sh->cpt;
+    if (sh->cpt > 4) return fail(AVR_E_CONFIG, "ray_reduce_bwd: T too long for this build");
+    sh->threads = max(64, ((nch + sh->cpt - 1) / sh->cpt + 63) / 64 * 64);
+    const int max_rays = min(kMaxRbRays, (int)(kLdsDefault / (12 + 4 * cb)));
+    // as launch_rb: many splits, at least 4 rays each
+    const int64_t wps = (int64_t)S * B * (sh->threads / 64);
+    auto rps_of = [&](int k) { return (R + k - 1) / k; };
+    int n = 1;
+    while (n < 256 && (n * wps < 262144 || rps_of(n) > max_rays) && rps_of(2 * n) >= 4) n *= 2;
+    sh->rps = rps_of(n);
+    if (sh->rps > max_rays) return fail(AVR_E_CONFIG, "ray_reduce_bwd: too many rays per split");
+    return 0;
+}
+
+template <typename Tin, bool VECTOR, int CB, bool ACCUM>
+int launch_rb_mc(const avr_render_params* p, int B, int C, int c0, const McBwdShape& sh, const void* sig,
+                 const float* gz, const float* w, const int32_t* delay, const float* gain, int64_t gstride,
+                 void* gsig, float* gw, hipStream_t st) {
+    const int R = n_rays(*p), S = p->n_samples, T = p->T;
+    const int64_t total = (int64_t)B * R * S * T;
+    const dim3 grid((R + sh.rps - 1) / sh.rps, S, B);
+    const size_t lds = (size_t)max(sh.rps, 1) * (12 + 4 * CB);
+    auto go = [&](auto c_tag) {
+        constexpr int CPT = decltype(c_tag)::value;
+        auto kern = sh.threads <= 512 ? ray_reduce_mc_bwd_kernel<Tin, VECTOR, CPT, CB, 512, ACCUM>
+                                      : ray_reduce_mc_bwd_kernel<Tin, VECTOR, CPT, CB, 1024, ACCUM>;
+        return launch("avr_ray_reduce_mc_bwd", kern, grid, dim3(sh.threads), lds, st, *p, (const Tin*)sig, gz, w,
+                      delay, gain, gstride, C, c0, (Tin*)gsig, gw, B, R, S, T, sh.rps, total);
+    };
+    switch (sh.cpt) {
+        case 1: return go(std::integral_constant<int, 1>{});
+        case 2: return go(std::integral_constant<int, 2>{});
+        case 3: return go(std::integral_constant<int, 3>{});
+        default: return go(std::integral_constant<int, 4>{});
+    }
+}
+
+// blocks of 4, then 2, then 1 channels; the first writes, the others add
+template <typename Tin, bool VECTOR>
+int launch_rb_mc_blocks(const avr_render_params* p, int B, int C, const void* sig, const float* gz, const float* w,
+                        const int32_t* delay, const float* gain, int64_t gstride, void* gsig, float* gw,
+                        hipStream_t st) {
+    constexpr int VEC = VECTOR ? Vec16<Tin>::N : 1;
+    McBwdShape sh;
+    if (int e = mc_bwd_shape<VEC>(p, B, mc_block(C), &sh)) return e;
+    for (int c0 = 0; c0 < C;) {
+        const int cb = mc_block(C - c0);
+        int e;
+#define AVR_RB_MC(CB)                                                                                          \
+    e = c0 == 0 ? launch_rb_mc<Tin, VECTOR, CB, false>(p, B, C, c0, sh, sig, gz, w, delay, gain, gstride, gsig, \
+                                                        gw, st)                                                \
+                : launch_rb_mc<Tin, VECTOR, CB, true>(p, B, C, c0, sh, sig, gz, w, delay, gain, gstride, gsig,  \
+                                                       gw, st)
+        if (cb == 4)
+            AVR_RB_MC(4);
+        else if (cb == 2)
+            AVR_RB_MC(2);
+        else
+            AVR_RB_MC(1);
+#undef AVR_RB_MC
+        if (e) return e;
+        c0 += cb;
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" int avr_ray_reduce_mc_bwd(const avr_render_params* p, int32_t B, int32_t C, const void* signal,
+                                     int32_t sig_dtype, const float* gz, const float* w, const int32_t* delay,
+                                     const float* gain, int64_t gain_b_stride, void* grad_signal, float* grad_w,
+                                     void* stream) {
+    AVR_REQUIRE(p && B >= 1 && signal && gz && w && delay && gain && grad_signal && grad_w,
+                "avr_ray_reduce_mc_bwd: bad args");
+    AVR_REQUIRE(C >= 1 && C <= 16, "avr_ray_reduce_mc_bwd: C must be 1..16");
+    AVR_REQUIRE(p->T >= 2 && p->T <= 16384, "avr_ray_reduce_mc_bwd: T out of range");
+    AVR_REQUIRE(gain_b_stride == 0 || gain_b_stride == (int64_t)C * n_rays(*p),
+                "avr_ray_reduce_mc_bwd: gain_b_stride must be 0 ([C,R]) or C*R ([B,C,R])");
+    const int64_t row = (int64_t)p->n_samples * p->T;
+    return dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16, AVR_DTYPE_BF16>(
+        sig_dtype, "avr_ray_reduce_mc_bwd", [&](auto tag) {
+            using Tin = typename decltype(tag)::type;
+            if (reinterpret_cast<uintptr_t>(signal) % 16 == 0 && reinterpret_cast<uintptr_t>(grad_signal) % 16 == 0 &&
+                row % Vec16<Tin>::N == 0)
+                return launch_rb_mc_blocks<Tin, true>(p, B, C, signal, gz, w, delay, gain, gain_b_stride,
+                                                      grad_signal, grad_w, as_stream(stream));
+            return launch_rb_mc_blocks<Tin, false>(p, B, C, signal, gz, w, delay, gain, gain_b_stride, grad_signal,
+                                                   grad_w, as_stream(stream));
         });
 }
 

@@ -467,6 +467,125 @@ __global__ __launch_bounds__(MAXT) void ray_reduce_fwd_kernel(
         }
 }
 
+// ------------------------------ the same stream with CB receiver channels
+// part[k][b*C + c0 + j][s][t] = sum_{r in split k} fl(w[b,r,s]*g[b,c0+j,r]) * [live] * x[b,r,s,t]
+// for j < CB: ray_reduce_fwd_kernel's twin with one column per group.  The
+// signal row is read once and feeds CB accumulator sets; per channel the
+// arithmetic is ray_reduce_fwd_kernel's on the weights w*g (the product is
+// rounded to fp32 once, while the split's slab is gathered), so a channel
+// equals the single-channel kernel run with w*g bit for bit.  LDS:
+// d_l[nr], then wg_l[CB][nr].
+template <typename Tin, bool VECTOR, int CPT, int kUnroll, int CB, int MAXT>
+__global__ __launch_bounds__(MAXT) void ray_reduce_mc_fwd_kernel(
+    avr_render_params pp, const Tin* __restrict__ sig, const float* __restrict__ w,
+    const int32_t* __restrict__ delay, const float* __restrict__ gain, int64_t gain_b_stride, int C,
+    int c0, float* __restrict__ part, int B, int R, int S, int T, int rays_per_split, int64_t total) {
+    constexpr int VEC = VECTOR ? Vec16<Tin>::N : 1;
+    extern __shared__ float lds_mc[];
+    const int nthreads = blockDim.x;
+    const int split = blockIdx.x, s = blockIdx.y, b = blockIdx.z;
+    const int r0 = split * rays_per_split;
+    const int nr = max(0, min(R, r0 + rays_per_split) - r0);
+    const int ld = max(nr, 1);
+    int* d_l = reinterpret_cast<int*>(lds_mc);
+    float* wg_l = lds_mc + ld;
+    const float* gb = gain + (int64_t)b * gain_b_stride + (int64_t)c0 * R + r0;
+    for (int i = threadIdx.x; i < nr; i += nthreads) {
+        const int64_t idx = ((int64_t)b * R + r0 + i) * S + s;
+        const float wv = w[idx];
+        d_l[i] = delay[idx];
+#pragma unroll
+        for (int j = 0; j < CB; ++j) wg_l[j * ld + i] = wv * gb[(int64_t)j * R + i];
+    }
+    __syncthreads();
+    // an empty split (nr == 0) falls through both loops and writes zeros
+    const int64_t row0 = (((int64_t)b * R + r0) * S + s) * (int64_t)T;
+    const int phase = (int)(row0 % VEC);
+    const int nchunks = (T + phase + VEC - 1) / VEC;
+    const int64_t row_stride = (int64_t)S * T;
+    const int lim = tail_limit(pp, s);
+
+    float acc[CB][CPT][VEC];
+    int tk[CPT][VEC];  // t of each slot (-1: outside the row)
+    int tm[CPT][VEC];  // t if inside the tail window t < T-1-shift[s], else -1
+    int tmax[CPT];     // per chunk: largest tm (-1: no live slot)
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) {
+        tmax[c] = -1;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+#pragma unroll
+            for (int j = 0; j < CB; ++j) acc[j][c][k] = 0.0f;
+            const int e = (threadIdx.x + c * nthreads) * VEC + k - phase;
+            tk[c][k] = (e >= 0 && e < T) ? e : -1;
+            tm[c][k] = (tk[c][k] >= 0 && tk[c][k] < lim) ? tk[c][k] : -1;
+            tmax[c] = max(tmax[c], tm[c][k]);
+        }
+    }
+
+    auto load_chunk = [&](int64_t rowbase, int c, bool need, float* x) {
+        const int j = threadIdx.x + c * nthreads;
+        if constexpr (VECTOR) {
+            // as ray_reduce_fwd_kernel: chunks lie inside the tensor, dead
+            // chunks and spare lanes read zeros without touching memory
+            load16_masked(sig + rowbase, (uint32_t)nchunks * 16u,
+                          need ? (uint32_t)j * 16u : kSkip, x);
+        } else {
+            const int64_t e0 = rowbase + j;
+            x[0] = (need && j < nchunks && e0 < total) ? load_f(sig, e0) : 0.0f;
+        }
+    };
+    auto accumulate = [&](int r, float (*x)[VEC]) {
+        const int ds = d_l[r];
+        float wg[CB];
+#pragma unroll
+        for (int j = 0; j < CB; ++j) wg[j] = wg_l[j * ld + r];
+#pragma unroll
+        for (int c = 0; c < CPT; ++c)
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                const bool on = tm[c][k] >= ds;
+#pragma unroll
+                for (int j = 0; j < CB; ++j)
+                    acc[j][c][k] = fmaf(on ? wg[j] : 0.0f, x[c][k], acc[j][c][k]);
+            }
+    };
+
+    int r = 0;
+    for (; r + kUnroll <= nr; r += kUnroll) {
+        float x[kUnroll][CPT][VEC];
+        bool need[kUnroll][CPT];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u)
+#pragma unroll
+            for (int c = 0; c < CPT; ++c) need[u][c] = tmax[c] >= d_l[r + u];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const int64_t rowbase = row0 + (int64_t)(r + u) * row_stride - phase;
+#pragma unroll
+            for (int c = 0; c < CPT; ++c) load_chunk(rowbase, c, need[u][c], x[u][c]);
+        }
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) accumulate(r + u, x[u]);
+    }
+    for (; r < nr; ++r) {
+        const int64_t rowbase = row0 + (int64_t)r * row_stride - phase;
+        float x[CPT][VEC];
+#pragma unroll
+        for (int c = 0; c < CPT; ++c) load_chunk(rowbase, c, tmax[c] >= d_l[r], x[c]);
+        accumulate(r, x);
+    }
+#pragma unroll
+    for (int j = 0; j < CB; ++j) {
+        float* pj = part + ((((int64_t)split * B + b) * C + c0 + j) * S + s) * (int64_t)T;
+#pragma unroll
+        for (int c = 0; c < CPT; ++c)
+#pragma unroll
+            for (int k = 0; k < VEC; ++k)
+                if (tk[c][k] >= 0) pj[tk[c][k]] = acc[j][c][k];
+    }
+}
+
 // ------------------------------- DFT + phase + sum over samples (MFMA f32)
 // C[s, (f,re|im)] = sum_t z[b,s,t] * tw[(t*f) mod T]  with v_mfma_f32_32x32x2_f32
 // (exact fp32 FMA chain).  A = z tile staged in LDS (32 samples x 64 t),
@@ -999,10 +1118,10 @@ int launch_reduce_any(const avr_render_params* p, int B, const void* sig, const 
 }
 }  // namespace
 
-extern "C" int avr_reduce_splits(const avr_render_params* p, int32_t B, int32_t sig_dtype,
-                                 int32_t* n_split) {
-    if (int e = validate(p)) return e;
-    AVR_REQUIRE(B >= 1 && n_split, "avr_reduce_splits: bad args");
+namespace {
+// The split rule of the ray reduction for `max_rays` rays per split at most
+// (the LDS slab of the kernel that will run).
+int choose_reduce_splits(const avr_render_params* p, int B, int sig_dtype, int max_rays, int32_t* n_split) {
     const int R = n_rays(*p), S = p->n_samples, T = p->T;
     const int vec = (sig_dtype == AVR_DTYPE_F16 || sig_dtype == AVR_DTYPE_BF16) ? 8 : 4;
     const ReduceShape sh = vec == 8 ? reduce_shape<8>(S, T) : reduce_shape<4>(S, T);
@@ -1010,7 +1129,7 @@ extern "C" int avr_reduce_splits(const avr_render_params* p, int32_t B, int32_t 
     auto rps = [&](int k) { return (R + k - 1) / k; };
     if (const char* f = getenv("AVR_NSPLIT")) {  // validated tuning knob: 1, 2, 4, 8 or 16 ray splits
         const int v = atoi(f);
-        if ((v == 1 || v == 2 || v == 4 || v == 8 || v == 16) && v <= R && rps(v) * sh.G <= kMaxGroupRays) {
+        if ((v == 1 || v == 2 || v == 4 || v == 8 || v == 16) && v <= R && rps(v) * sh.G <= max_rays) {
             *n_split = v;
             return 0;
         }
@@ -1022,12 +1141,20 @@ extern "C" int avr_reduce_splits(const avr_render_params* p, int32_t B, int32_t 
     const int64_t waves_target = (vec == 8) ? 4096 : 1536;
     const int64_t waves_per_split = (int64_t)groups * B * (sh.threads / 64);
     int n = 1;
-    while (n < 16 && (n * waves_per_split < waves_target || rps(n) * sh.G > kMaxGroupRays) &&
+    while (n < 16 && (n * waves_per_split < waves_target || rps(n) * sh.G > max_rays) &&
            rps(2 * n) >= 8)
         n *= 2;
-    if (rps(n) * sh.G > kMaxGroupRays) return fail(AVR_E_CONFIG, "avr_reduce_splits: too many rays");
+    if (rps(n) * sh.G > max_rays) return fail(AVR_E_CONFIG, "avr_reduce_splits: too many rays");
     *n_split = n;
     return 0;
+}
+}  // namespace
+
+extern "C" int avr_reduce_splits(const avr_render_params* p, int32_t B, int32_t sig_dtype,
+                                 int32_t* n_split) {
+    if (int e = validate(p)) return e;
+    AVR_REQUIRE(B >= 1 && n_split, "avr_reduce_splits: bad args");
+    return choose_reduce_splits(p, B, sig_dtype, kMaxGroupRays, n_split);
 }
 
 extern "C" int avr_ray_reduce_fwd(const avr_render_params* p, int32_t B, const void* signal,
@@ -1043,6 +1170,100 @@ extern "C" int avr_ray_reduce_fwd(const avr_render_params* p, int32_t B, const v
         sig_dtype, "avr_ray_reduce_fwd", [&](auto tag) {
             return launch_reduce_any<typename decltype(tag)::type>(p, B, signal, w, delay, n_split, part,
                                                                   as_stream(stream));
+        });
+}
+
+// ---- C receiver channels: per-ray gains on the ray sum, one stream per block
+namespace {
+constexpr int kMaxChannels = 16;
+constexpr int mc_block(int left) { return left >= 4 ? 4 : left >= 2 ? 2 : 1; }
+// Rays per split of a C-channel call: the slab of its widest channel block,
+// (4 + 4*CB) bytes per ray, stays within the 64 KiB a launch gets unasked.
+constexpr int mc_max_rays(int C) {
+    const int fit = (int)(kLdsDefault / (4 + 4 * mc_block(C)));
+    return fit < kMaxGroupRays ? fit : kMaxGroupRays;
+}
+
+template <typename Tin, bool VECTOR, int CB>
+int launch_reduce_mc(const avr_render_params* p, int B, int C, int c0, const void* sig, const float* w,
+                     const int32_t* delay, const float* gain, int64_t gstride, int n_split, float* part,
+                     hipStream_t st) {
+    constexpr int VEC = VECTOR ? Vec16<Tin>::N : 1;
+    const int R = n_rays(*p), S = p->n_samples, T = p->T;
+    const int rps = (R + n_split - 1) / n_split;
+    const ReduceShape sh = reduce_shape<VEC>(S, T);
+    const int64_t total = (int64_t)B * R * S * T;
+    const dim3 grid(n_split, S, B);
+    const dim3 block(sh.threads);
+    const size_t lds = (size_t)max(rps, 1) * (4 + 4 * CB);
+    auto go = [&](auto c_tag) {
+        constexpr int CPT = decltype(c_tag)::value;
+        auto kern = block.x <= 512 ? ray_reduce_mc_fwd_kernel<Tin, VECTOR, CPT, kReduceRows, CB, 512>
+                                   : ray_reduce_mc_fwd_kernel<Tin, VECTOR, CPT, kReduceRows, CB, 1024>;
+        return launch("avr_ray_reduce_mc_fwd", kern, grid, block, lds, st, *p, (const Tin*)sig, w, delay, gain,
+                      gstride, C, c0, part, B, R, S, T, rps, total);
+    };
+    switch (sh.cpt) {
+        case 1: return go(std::integral_constant<int, 1>{});
+        case 2: return go(std::integral_constant<int, 2>{});
+        case 3: return go(std::integral_constant<int, 3>{});
+        case 4: return go(std::integral_constant<int, 4>{});
+    }
+    return fail(AVR_E_CONFIG, "ray_reduce: T too long for this build");
+}
+
+// all C channels in blocks of 4, then 2, then 1
+template <typename Tin, bool VECTOR>
+int launch_reduce_mc_blocks(const avr_render_params* p, int B, int C, const void* sig, const float* w,
+                            const int32_t* delay, const float* gain, int64_t gstride, int n_split, float* part,
+                            hipStream_t st) {
+    for (int c0 = 0; c0 < C;) {
+        const int cb = mc_block(C - c0);
+        int e;
+        if (cb == 4)
+            e = launch_reduce_mc<Tin, VECTOR, 4>(p, B, C, c0, sig, w, delay, gain, gstride, n_split, part, st);
+        else if (cb == 2)
+            e = launch_reduce_mc<Tin, VECTOR, 2>(p, B, C, c0, sig, w, delay, gain, gstride, n_split, part, st);
+        else
+            e = launch_reduce_mc<Tin, VECTOR, 1>(p, B, C, c0, sig, w, delay, gain, gstride, n_split, part, st);
+        if (e) return e;
+        c0 += cb;
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" int avr_reduce_mc_splits(const avr_render_params* p, int32_t B, int32_t C, int32_t sig_dtype,
+                                    int32_t* n_split, int32_t* max_rays) {
+    if (int e = validate(p)) return e;
+    AVR_REQUIRE(B >= 1 && n_split, "avr_reduce_mc_splits: bad args");
+    AVR_REQUIRE(C >= 1 && C <= kMaxChannels, "avr_reduce_mc_splits: C must be 1..16");
+    if (max_rays) *max_rays = mc_max_rays(C);
+    return choose_reduce_splits(p, B, sig_dtype, mc_max_rays(C), n_split);
+}
+
+extern "C" int avr_ray_reduce_mc_fwd(const avr_render_params* p, int32_t B, int32_t C, const void* signal,
+                                     int32_t sig_dtype, const float* w, const int32_t* delay,
+                                     const float* gain, int64_t gain_b_stride, int32_t n_split, float* part,
+                                     void* stream) {
+    if (int e = validate(p)) return e;
+    AVR_REQUIRE(B >= 1 && signal && w && delay && gain && part, "avr_ray_reduce_mc_fwd: null pointer");
+    AVR_REQUIRE(C >= 1 && C <= kMaxChannels, "avr_ray_reduce_mc_fwd: C must be 1..16");
+    const int R = n_rays(*p);
+    AVR_REQUIRE(gain_b_stride == 0 || gain_b_stride == (int64_t)C * R,
+                "avr_ray_reduce_mc_fwd: gain_b_stride must be 0 ([C,R]) or C*R ([B,C,R])");
+    AVR_REQUIRE(n_split >= 1 && n_split <= R, "avr_ray_reduce_mc_fwd: n_split out of range");
+    AVR_REQUIRE((R + n_split - 1) / n_split <= mc_max_rays(C),
+                "avr_ray_reduce_mc_fwd: too many rays per split (raise n_split)");
+    const int64_t row = (int64_t)p->n_samples * p->T;
+    return dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16, AVR_DTYPE_BF16>(
+        sig_dtype, "avr_ray_reduce_mc_fwd", [&](auto tag) {
+            using Tin = typename decltype(tag)::type;
+            if (reinterpret_cast<uintptr_t>(signal) % 16 == 0 && row % Vec16<Tin>::N == 0)
+                return launch_reduce_mc_blocks<Tin, true>(p, B, C, signal, w, delay, gain, gain_b_stride, n_split,
+                                                          part, as_stream(stream));
+            return launch_reduce_mc_blocks<Tin, false>(p, B, C, signal, w, delay, gain, gain_b_stride, n_split,
+                                                       part, as_stream(stream));
         });
 }
 

@@ -127,10 +127,13 @@ class GraphedRender:
             r._staged = None
         return g
 
-    def render_ir(self, rays_o, position_tx, direction_tx=None):
+    def render_ir(self, rays_o, position_tx, direction_tx=None, *, ray_gain=None):
         """(spectrum [B, F, 2], IR [B, 2(F-1)]) as `AVRRender.render_ir`,
         replayed; the tensors are the instance's static outputs.  Host
         (CPU) pose tensors take the staged path, device ones one copy."""
+        if ray_gain is not None:
+            raise NotImplementedError("GraphedRender does not take ray_gain (directional receivers "
+                                      "render through AVRRender)")
         r = self.renderer
         # the device without r._device's availability check and torch.device
         # construction on every call (~1 us of the serial pose); a host pose

@@ -9,6 +9,9 @@ Mirrors `renderer.py` of the reference (KMASAHIRO/AVR):
   — renderer.py:31-124.  `ch_idx` is passed to `network_fn` only when it is
   not None (the reference always passes it, which `AVRModel_complex.forward`
   (model.py:291) rejects).
+* keyword-only `ray_gain` on `forward` / `render_ir` (not in the reference):
+  a directional receiver as per-ray gains, output [B, C, F, 2]
+  (`RenderCoreMC`, `avr_amd.spatial`).
 * module functions `ray_directions`, `normalize_points`,
   `denormalize_points` with the reference's names (renderer.py:127-165).
 
@@ -286,6 +289,101 @@ class RenderCore(torch.autograd.Function):
                 None, None, None, None, None, None, None)
 
 
+# --------------------------------------------------------------------------
+# directional receivers: per-ray gains g[c, r] on the ray sum
+# --------------------------------------------------------------------------
+def reduce_mc_splits(p, B, C, sig_code):
+    """(ray splits, most rays per split) of a C-channel ray reduction."""
+    n, cap = ctypes.c_int32(0), ctypes.c_int32(0)
+    _lib.call("avr_reduce_mc_splits", ctypes_ref(p), B, C, sig_code, ctypes.byref(n), ctypes.byref(cap))
+    return int(n.value), int(cap.value)
+
+
+def resolve_ray_gain(ray_gain, geom):
+    """`ray_gain` ([R], [C,R], [B,C,R] or a callable on this call's ray
+    directions) -> (fp32 contiguous device tensor [C,R] or [B,C,R], whether
+    the caller gave a single channel without a channel axis)."""
+    dev, B, R = geom["device"], geom["B"], geom["n_rays"]
+    g = ray_gain(geom["dirs"]) if callable(ray_gain) else ray_gain
+    g = _f32_on(torch.as_tensor(g).detach(), dev)
+    flat = g.dim() == 1
+    if flat:
+        g = g.unsqueeze(0)
+    if g.dim() not in (2, 3) or g.size(-1) != R or (g.dim() == 3 and g.size(0) != B):
+        raise ValueError(f"ray_gain has shape {tuple(g.shape)}; expected [{R}], [C,{R}] or [{B},C,{R}]")
+    C = g.size(-2)
+    if not 1 <= C <= 16:
+        raise ValueError(f"ray_gain has {C} channels; 1 to 16 are supported")
+    return g, flat
+
+
+def _gain_stride(gain):
+    return gain.size(1) * gain.size(2) if gain.dim() == 3 else 0
+
+
+def _render_core_mc_fwd(attn, signal, gain, p, tables, rays_o, position_tx, dirs):
+    """Stage calls of a C-channel render -> (out [B*C, F, 2], w, delay,
+    weights the C = 1 backward multiplies by).  One channel runs the
+    single-channel reduction on w*g; more run avr_ray_reduce_mc_fwd, which
+    reads the signal once per block of up to four channels."""
+    dev = signal.device
+    B, C = signal.size(0), gain.size(-2)
+    S, T = p.n_samples, p.T
+    st = _stream(dev)
+    sig_code = _dtype_code(signal)
+    w, delay = _weights(p, attn, rays_o, position_tx, dirs, tables, st)
+    if C == 1:
+        n_split = reduce_splits(p, B, sig_code)
+        wg = w * gain.reshape(-1, p.n_rays, 1)
+        part = torch.empty(n_split, B, S, T, dtype=torch.float32, device=dev)
+        _lib.call("avr_ray_reduce_fwd", ctypes_ref(p), B, _ptr(signal), sig_code, _ptr(wg), _ptr(delay),
+                  n_split, _ptr(part), st)
+    else:
+        n_split, _ = reduce_mc_splits(p, B, C, sig_code)
+        wg = w
+        part = torch.empty(n_split, B * C, S, T, dtype=torch.float32, device=dev)
+        _lib.call("avr_ray_reduce_mc_fwd", ctypes_ref(p), B, C, _ptr(signal), sig_code, _ptr(w), _ptr(delay),
+                  _ptr(gain), _gain_stride(gain), n_split, _ptr(part), st)
+    return _spectrum(p, tables, part, n_split, B * C, dev, st), wg, delay
+
+
+class RenderCoreMC(torch.autograd.Function):
+    """RenderCore for a directional receiver: `gain` [C, R] or [B, C, R] (fp32)
+    weights ray r of channel c.  Output [B, C, F, 2]; gradients to attn and
+    signal (gains are constants, like the poses)."""
+
+    @staticmethod
+    def forward(ctx, attn, signal, gain, p, tables, rays_o, position_tx, dirs):
+        out, wg, delay = _render_core_mc_fwd(attn, signal, gain, p, tables, rays_o, position_tx, dirs)
+        ctx.p, ctx.tables = p, tables
+        ctx.save_for_backward(attn, signal, gain, wg, delay)
+        return out.view(signal.size(0), gain.size(-2), -1, 2)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        attn, signal, gain, wg, delay = ctx.saved_tensors
+        p, tables = ctx.p, ctx.tables
+        dev = signal.device
+        B, C = signal.size(0), gain.size(-2)
+        R, S = p.n_rays, p.n_samples
+        st = _stream(dev)
+        gz = _grad_z(p, tables, grad_out.reshape(B * C, -1, 2), B * C, dev, st)
+        grad_signal = torch.empty_like(signal)
+        grad_w = torch.empty(B, R, S, dtype=torch.float32, device=dev)
+        if C == 1:
+            # wg = w*g: grad_signal is complete, grad_w lacks the factor g
+            _lib.call("avr_ray_reduce_bwd", ctypes_ref(p), B, _ptr(signal), _dtype_code(signal),
+                      _ptr(gz), _ptr(wg), _ptr(delay), _ptr(grad_signal), _ptr(grad_w), st)
+            grad_w = grad_w * gain.reshape(-1, R, 1)
+        else:
+            _lib.call("avr_ray_reduce_mc_bwd", ctypes_ref(p), B, C, _ptr(signal), _dtype_code(signal),
+                      _ptr(gz), _ptr(wg), _ptr(delay), _ptr(gain), _gain_stride(gain), _ptr(grad_signal),
+                      _ptr(grad_w), st)
+        grad_attn = _grad_attn(p, tables, attn, grad_w, st) if ctx.needs_input_grad[0] else None
+        return (grad_attn, grad_signal if ctx.needs_input_grad[1] else None,
+                None, None, None, None, None, None)
+
+
 def _packed_head_weight(w_master, W, cache, pref, shape_key, st):
     """W in avr_head_fwd's block-major layout (avr_head_pack_w).  With
     `cache` (no autograd graph recorded) the copy is kept on the master
@@ -330,7 +428,7 @@ class FusedHeadCore(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, attn, h, w_master, dtype, p, tables, rays_o, position_tx, dirs, cache=False, exact=False,
-                relu_h=False, timer=None):
+                relu_h=False, timer=None, gain=None):
         dev = h.device
         B, K = h.size(0), h.size(-1)
         S, T = p.n_samples, p.T
@@ -340,6 +438,10 @@ class FusedHeadCore(torch.autograd.Function):
         code = _dtype_code(h)
         w, delay = _weights(p, attn, rays_o, position_tx, dirs, tables, st)
         R = p.n_rays
+        if gain is not None:
+            # a one-channel receiver pattern [1 or B, R]: the head kernels sum
+            # the rays with the weights w*g
+            w = w * gain.unsqueeze(-1)
         perm = torch.empty(B, S, R, dtype=torch.int32, device=dev)
         ws = torch.empty(B, S, R, dtype=torch.float32, device=dev)
         cnt = torch.empty(B, S, T, dtype=torch.int32, device=dev)
@@ -370,7 +472,7 @@ class FusedHeadCore(torch.autograd.Function):
             _lib.call("avr_head_fwd", pref, B, K, _ptr(h), _ptr(Wp), code, _ptr(perm), _ptr(ws), _ptr(cnt),
                       n_split, _ptr(part), st)
         out = _spectrum(p, tables, part, n_split, B, dev, st)
-        ctx.p, ctx.tables, ctx.relu_h = p, tables, relu_h
+        ctx.p, ctx.tables, ctx.relu_h, ctx.gain = p, tables, relu_h, gain
         ctx.save_for_backward(attn, h, W, w, delay, perm, ws, cnt)
         return out
 
@@ -396,10 +498,12 @@ class FusedHeadCore(torch.autograd.Function):
         _lib.call("avr_head_bwd2", pref, B, K, _ptr(h), _ptr(W), code, _ptr(w), _ptr(delay), _ptr(perm),
                   _ptr(ws), _ptr(cnt), _ptr(gz), int(ctx.relu_h), _ptr(grad_h), _ptr(grad_w), _ptr(grad_W),
                   _ptr(work), nbytes.value, st)
+        if ctx.gain is not None:
+            grad_w = grad_w * ctx.gain.unsqueeze(-1)
         grad_attn = _grad_attn(p, tables, attn, grad_w, st) if ctx.needs_input_grad[0] else None
         return (grad_attn, grad_h if ctx.needs_input_grad[1] else None,
                 grad_W if ctx.needs_input_grad[2] else None, None, None, None, None, None, None, None, None, None,
-                None)
+                None, None)
 
 
 def _poison_nonfinite(out, tensors, ir_out=None):
@@ -618,9 +722,12 @@ class AVRRender(nn.Module):
                     self._pcache[key] = p
         return p
 
-    def render_from_network_output(self, attn, signal, geom, ir_out=None):
+    def render_from_network_output(self, attn, signal, geom, ir_out=None, *, ray_gain=None):
         """Render core (renderer.py:74-124) on given network outputs; the IR
-        (utils/criterion.py:71) is also written into `ir_out` when given."""
+        (utils/criterion.py:71) is also written into `ir_out` when given.
+        `ray_gain` ([R], [C,R], [B,C,R] or a callable on geom["dirs"]): a
+        directional receiver, out [B, C, F, 2] and ir_out [B, C, 2(F-1)]
+        ([B, F, 2] for a 1-D gain)."""
         dev, B = geom["device"], geom["B"]
         S = int(self.n_samples)
         native = (torch.float32, torch.float16, torch.bfloat16)
@@ -647,6 +754,19 @@ class AVRRender(nn.Module):
         with _on(dev):
             tables = get_tables(p, dev)
             check_config(p, tables)
+            if ray_gain is not None:
+                gain, flat = resolve_ray_gain(ray_gain, geom)
+                C, F = gain.size(-2), T // 2 + 1
+                args = (attn, signal, gain, p, tables, geom["rays_o"], geom["position_tx"], geom["dirs"])
+                if not (torch.is_grad_enabled() and (attn.requires_grad or signal.requires_grad)):
+                    out = _render_core_mc_fwd(*args)[0].view(B, C, F, 2)
+                else:
+                    out = RenderCoreMC.apply(*args)
+                if ir_out is not None:
+                    _lib.call("avr_irfft", B * C, F, _ptr(out), _ptr(tables.ir_twiddle), _ptr(ir_out), _stream(dev))
+                if self.propagate_nonfinite:
+                    out = _poison_nonfinite(out, (attn, signal), ir_out)
+                return out[:, 0] if flat else out
             if not (torch.is_grad_enabled() and (attn.requires_grad or signal.requires_grad)):
                 # inference: the same native call without the autograd node
                 out = _render_core_fwd(attn, signal, p, tables, geom["rays_o"],
@@ -680,13 +800,15 @@ class AVRRender(nn.Module):
         """The output-rounding-exact head runs for 16-bit networks (csrc/head_exact.hip)."""
         return self.exact_head and dtype in (torch.float16, torch.bfloat16) and K % 16 == 0 and K <= 512
 
-    def render_from_hidden(self, attn, h, weight, dtype, geom, relu_link=None):
+    def render_from_hidden(self, attn, h, weight, dtype, geom, relu_link=None, gain=None):
         """Render core with the signal head fused (FusedHeadCore): `h` is the
         signal network's last hidden activation [B, R*S, K], `weight` its
         last layer's weight [T, K] (signal = h @ weight^T).  `relu_link`
         (the network's, see model.MLP.hidden): h is a ReLU output the head
         alone consumes; the head's backward then applies that ReLU's mask
-        and the link tells the layer to skip its own."""
+        and the link tells the layer to skip its own.  `gain` [1 or B, R]
+        (fp32, on the device): a one-channel receiver pattern folded into
+        the compositing weights."""
         dev, B = geom["device"], geom["B"]
         S = int(self.n_samples)
         attn = attn.to(dev).reshape(B, -1)
@@ -706,7 +828,7 @@ class AVRRender(nn.Module):
             relu_h = relu_link is not None and torch.is_grad_enabled()
             out = FusedHeadCore.apply(attn, h, weight, dtype, p, tables, geom["rays_o"],
                                       geom["position_tx"], geom["dirs"], not torch.is_grad_enabled(), exact,
-                                      relu_h, self.kernel_timer)
+                                      relu_h, self.kernel_timer, gain)
             if relu_h:
                 relu_link[0] = True
             if self.propagate_nonfinite:
@@ -716,27 +838,46 @@ class AVRRender(nn.Module):
                 out = _poison_nonfinite(out, (attn, h, weight))
             return out
 
-    def forward(self, rays_o, position_tx, direction_tx=None, ch_idx=None):
-        """Render [B, F, 2] (real, imag) spectra; see renderer.py:31-124."""
-        return self._render(rays_o, position_tx, direction_tx, ch_idx, None)
+    def forward(self, rays_o, position_tx, direction_tx=None, ch_idx=None, *, ray_gain=None):
+        """Render [B, F, 2] (real, imag) spectra; see renderer.py:31-124.
 
-    def render_ir(self, rays_o, position_tx, direction_tx=None, ch_idx=None):
+        `ray_gain`: a directional receiver, the per-ray gains g[c, r] on the
+        ray sum (avr_amd.spatial builds the usual patterns) as a tensor [R],
+        [C, R] or [B, C, R], or a callable `dirs [R, 3] -> tensor` called on
+        the device with this call's jittered directions.  The output is then
+        [B, C, F, 2] ([B, F, 2] for a 1-D gain); None renders the
+        omnidirectional receiver as before."""
+        return self._render(rays_o, position_tx, direction_tx, ch_idx, None, ray_gain=ray_gain)
+
+    def render_ir(self, rays_o, position_tx, direction_tx=None, ch_idx=None, *, ray_gain=None):
         """(spectrum [B, F, 2], IR [B, 2(F-1)]): forward plus
         `torch.real(torch.fft.irfft(...))` (utils/criterion.py:71).  Without
         autograd the IR is computed in the same native call; with autograd
-        recording it is spectrum_to_ir(out), which differentiates."""
+        recording it is spectrum_to_ir(out), which differentiates.  With
+        `ray_gain` (see forward) both carry the channel axis: [B, C, F, 2]
+        and [B, C, 2(F-1)]."""
         ir = []
         # the IR inside the render's native call is a forward-only side
         # output; with autograd recording, take it differentiably instead
         grad = torch.is_grad_enabled()
-        out = self._render(rays_o, position_tx, direction_tx, ch_idx, None if grad else ir)
-        return out, (ir[0] if ir else spectrum_to_ir(out))
+        out = self._render(rays_o, position_tx, direction_tx, ch_idx, None if grad else ir, ray_gain=ray_gain)
+        if ir:
+            return out, ir[0]
+        if out.dim() == 4:
+            B, C, F = out.shape[:3]
+            return out, spectrum_to_ir(out.reshape(B * C, F, 2)).view(B, C, -1)
+        return out, spectrum_to_ir(out)
 
-    def _render(self, rays_o, position_tx, direction_tx, ch_idx, ir_slot, u_azi=None):
+    def _render(self, rays_o, position_tx, direction_tx, ch_idx, ir_slot, u_azi=None, ray_gain=None):
         """Sampling -> network -> render core; `u_azi` (the azimuth jitter,
         host or device) replaces the CPU draw, as RayShardedRender passes
         rank 0's broadcast draw so every ray shard sees one sphere."""
         pts, view, tx, dtx, geom = self.sample(rays_o, position_tx, direction_tx, u_azi=u_azi)
+        gain = flat = None
+        if ray_gain is not None:
+            if self.ray_range is not None:
+                raise NotImplementedError("ray_gain with sharded rays")
+            gain, flat = resolve_ray_gain(ray_gain, geom)
         kw = {} if ch_idx is None else {"ch_idx": ch_idx}
         if getattr(self.network_fn, "accepts_ray_layout", False):
             # our own networks: tell them which inputs repeat over samples /
@@ -745,25 +886,42 @@ class AVRRender(nn.Module):
         net_in = (pts, view, tx) if dtx is None else (pts, view, tx, dtx)
         if self.fused_head and getattr(self.network_fn, "supports_fused_head", False):
             attn, h, weight, dtype = self.network_fn.forward_fused(*net_in, **kw)
-            if self._head_supported(geom, h, weight, dtype):
+            # one receiver channel folds into the head's compositing weights;
+            # more take the network's last layer and the multi-channel core
+            if (gain is None or gain.size(-2) == 1) and self._head_supported(geom, h, weight, dtype):
                 # our own networks leave the link of h's ReLU (model.MLP.hidden)
                 link = getattr(self.network_fn, "_relu_link", None) if self.head_relu_link else None
                 self.network_fn.__dict__.pop("_relu_link", None)
-                return self.render_from_hidden(attn, h, weight, dtype, geom, link)
+                out = self.render_from_hidden(attn, h, weight, dtype, geom, link,
+                                              None if gain is None else gain.squeeze(-2))
+                return out if gain is None or flat else out.unsqueeze(1)
             signal = self.network_fn.finish_signal(h)
-            return self.render_from_network_output(attn, signal, geom)
+            if gain is None:
+                return self.render_from_network_output(attn, signal, geom)
+            return self.render_from_network_output(attn, signal, geom, self._ir_out(signal, geom, gain, flat, ir_slot),
+                                                   ray_gain=gain[0] if flat else gain)
         if dtx is not None:
             attn, signal = self.network_fn(pts, view, tx, dtx, **kw)
         else:
             attn, signal = self.network_fn(pts, view, tx, **kw)
-        ir_out = None
-        if ir_slot is not None:
-            F = signal.size(-1) // 2 + 1
-            if F >= 2:
-                ir_out = torch.empty(geom["B"], 2 * (F - 1), dtype=torch.float32,
-                                     device=geom["device"])
-                ir_slot.append(ir_out)
-        return self.render_from_network_output(attn, signal, geom, ir_out)
+        ir_out = self._ir_out(signal, geom, gain, flat, ir_slot)
+        if gain is None:
+            return self.render_from_network_output(attn, signal, geom, ir_out)
+        return self.render_from_network_output(attn, signal, geom, ir_out, ray_gain=gain[0] if flat else gain)
+
+    @staticmethod
+    def _ir_out(signal, geom, gain, flat, ir_slot):
+        """The IR buffer of a render_ir call without autograd ([B, n], or
+        [B, C, n] under a gain with a channel axis), appended to `ir_slot`."""
+        if ir_slot is None:
+            return None
+        F = signal.size(-1) // 2 + 1
+        if F < 2:
+            return None
+        lead = (geom["B"],) if gain is None or flat else (geom["B"], gain.size(-2))
+        ir_out = torch.empty(*lead, 2 * (F - 1), dtype=torch.float32, device=geom["device"])
+        ir_slot.append(ir_out)
+        return ir_out
 
 
 # --------------------------------------------------------------------------

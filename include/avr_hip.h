@@ -166,6 +166,27 @@ int avr_ray_reduce_fwd(const avr_render_params* p, int32_t B, const void* signal
  * of two <= 16); the caller sizes `part` with it. */
 int avr_reduce_splits(const avr_render_params* p, int32_t B, int32_t sig_dtype, int32_t* n_split);
 
+/* ---- directional receivers: C channels of per-ray gains, one stream ----
+ * part[n_split][B*C][S][T] (channel minor to pose) = sum over the rays of
+ * split k of fl(w[b,r,s] * gain[b,c,r]) * [live window] * signal[b,r,s,t],
+ * 1 <= C <= 16.  gain is fp32 [C][R] (gain_b_stride = 0, shared by the poses)
+ * or [B][C][R] (gain_b_stride = C*R).  The signal is read once per block of
+ * 4, 2 or 1 channels (C = 5: 4 + 1); channel c equals avr_ray_reduce_fwd run
+ * with the weights w*gain[c] at the same n_split bit for bit.  Everything
+ * downstream (avr_dft_phase_fwd, avr_spectrum_finalize, avr_irfft) takes
+ * `part` with batch B*C.  The rays of a split are bounded by the LDS slab of
+ * the widest block, see avr_reduce_mc_splits; more are AVR_E_ARG before any
+ * launch. */
+int avr_ray_reduce_mc_fwd(const avr_render_params* p, int32_t B, int32_t C, const void* signal,
+                          int32_t sig_dtype, const float* w, const int32_t* delay,
+                          const float* gain, int64_t gain_b_stride, int32_t n_split, float* part,
+                          void* stream);
+
+/* avr_reduce_splits' rule for a C-channel call, and (max_rays, may be NULL)
+ * the most rays one split of such a call may hold. */
+int avr_reduce_mc_splits(const avr_render_params* p, int32_t B, int32_t C, int32_t sig_dtype,
+                         int32_t* n_split, int32_t* max_rays);
+
 /* ---- a9/a10/a11/a12 (frequency half): DFT + phase + sum over samples ---
  * z[b,s,t] = pl[shift[s]+t] * [t < T-1-shift[s]] * sum_k part[k,b,s,t]
  * spart[B][P][F][2], P = ceil(S/32) * k_split: partial spectra
@@ -239,6 +260,16 @@ int avr_dft_phase_bwd(const avr_render_params* p, int32_t B, const float* grad_o
 int avr_ray_reduce_bwd(const avr_render_params* p, int32_t B, const void* signal,
                        int32_t sig_dtype, const float* gz, const float* w,
                        const int32_t* delay, void* grad_signal, float* grad_w, void* stream);
+
+/* Adjoint of avr_ray_reduce_mc_fwd: gz[B*C][S][T] (avr_dft_phase_bwd with
+ * batch B*C), with q[b,r,s,t] = sum_c gain[b,c,r] * gz[b*C+c,s,t]:
+ * grad_signal = w * m * q, grad_w = sum_t m * q * signal.  One launch per
+ * block of at most 4 channels; the first writes, later ones add into
+ * grad_signal and grad_w.  Gains are constants (no gradient). */
+int avr_ray_reduce_mc_bwd(const avr_render_params* p, int32_t B, int32_t C, const void* signal,
+                          int32_t sig_dtype, const float* gz, const float* w, const int32_t* delay,
+                          const float* gain, int64_t gain_b_stride, void* grad_signal, float* grad_w,
+                          void* stream);
 
 /* grad_w -> grad_attn[B][R*S] (attn dtype): adjoint of the transmittance
  * scan and of alpha = 1 - exp(-attn*dist). */
