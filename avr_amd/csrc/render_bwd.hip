@@ -8,6 +8,7 @@
 //   weights_bwd:    adjoint of w = T_s*alpha_s (suffix affine scan) and of
 //                   alpha = 1-exp(-attn*dist)
 #include "common.h"
+#include "ray_stream.h"
 
 using namespace avr;
 
@@ -106,9 +107,6 @@ __global__ __launch_bounds__(kBwdThreads) void dft_phase_bwd_kernel(
 }
 
 // -------------------------------------------------- ray reduce backward
-constexpr int kMaxRbThreads = 1024;
-constexpr int kMaxRbRays = 4096;  // G * rays per split
-
 // The forward reduction's twin: one workgroup per (ray split, column group of
 // G samples, b) streams the group's contiguous super-rows ray by ray.  Each
 // lane keeps gz for its fixed (g, t) chunk slots in registers, reads the
@@ -117,7 +115,7 @@ constexpr int kMaxRbRays = 4096;  // G * rays per split
 // its share of grad_w = sum_t [t>=delay]*gz*x, reduced per ray by a wave
 // shuffle tree and one LDS atomic per wave.  Four rays' loads are issued
 // before any of them is consumed.
-template <typename Tin, bool VECTOR, int CPT, int G, int MAXT, bool NTS>
+template <typename Tin, bool VECTOR, int CPT, int G, int MAXT>
 __global__ __launch_bounds__(MAXT) void ray_reduce_bwd_kernel(
     avr_render_params pp, const Tin* __restrict__ sig, const float* __restrict__ gz, const float* __restrict__ w,
     const int32_t* __restrict__ delay, Tin* __restrict__ gsig, float* __restrict__ gw, int B,
@@ -240,12 +238,8 @@ __global__ __launch_bounds__(MAXT) void ray_reduce_bwd_kernel(
             const int j = threadIdx.x + c * nthreads;
             const int64_t e0 = rowbase + (int64_t)j * VEC;
             if (VECTOR && full[c]) {
-                if constexpr (VECTOR) {
-                    if constexpr (NTS)
-                        store16_nt(gsig + e0, o);
-                    else
-                        store16(gsig + e0, o);
-                }
+                // streaming store: grad_x is not read back (profiles/r01_tune_bwd_*.jsonl)
+                if constexpr (VECTOR) store16_nt(gsig + e0, o);
             } else {
 #pragma unroll
                 for (int k = 0; k < VEC; ++k)
@@ -555,60 +549,47 @@ extern "C" int avr_dft_phase_bwd(const avr_render_params* p, int32_t B, const fl
 }
 
 namespace {
+// Ray splits of a backward launch: no partials in the backward, so splits
+// cost only a gz re-read from L2: take many (best at the 256-split cap,
+// profiles/r01_tune_bwd_*.jsonl), at least 4 rays each, a split's slab of
+// `max_rays` rays at most.  Returns the rays per split.
+int rb_rays_per_split(int R, int64_t waves_per_split, int max_rays) {
+    const int64_t waves_target = 262144;
+    auto rps_of = [&](int k) { return (R + k - 1) / k; };
+    int n = 1;
+    while (n < 256 && (n * waves_per_split < waves_target || rps_of(n) > max_rays) && rps_of(2 * n) >= 4) n *= 2;
+    return rps_of(n);
+}
+
 template <typename Tin, bool VECTOR>
 int launch_rb(const avr_render_params* p, int B, const void* sig, const float* gz, const float* w,
               const int32_t* delay, void* gsig, float* gw, hipStream_t st) {
     constexpr int VEC = VECTOR ? Vec16<Tin>::N : 1;
     const int R = n_rays(*p), S = p->n_samples, T = p->T;
-    // same super-row shape rule as the forward reduction
+    // Column groups of G = 1, 2 or 4 samples, so that a super-row is up to
+    // 512 (16-bit: 256) chunks.  The forward runs G = 1 only; here G = 2 is
+    // what T = 1022 (config 2) runs.  The block shape is the stream's rule.
     int G = 1;
     const int max_chunks = (VEC == 8) ? 256 : 512;
     while (G < 4 && 2 * G * T <= max_chunks * VEC && 2 * G <= S) G *= 2;
-    int max_phase = 0;
-    for (int s0 = 0; s0 < S && s0 < VEC * G; s0 += G)
-        max_phase = max(max_phase, (int)(((int64_t)s0 * T) % VEC));
-    const int nch = (G * T + max_phase + VEC - 1) / VEC;
-    int cpt = 1;
-    while ((nch + cpt - 1) / cpt > kMaxRbThreads) ++cpt;
-    const int threads = max(64, ((nch + cpt - 1) / cpt + 63) / 64 * 64);
+    const StreamShape sh = stream_shape<VEC>(S, T, G);
     const int groups = (S + G - 1) / G;
-    // rays per split within the LDS slab, at least 4 per split
-    int n = 1;
-    const int64_t wps = (int64_t)groups * B * (threads / 64);
-    // no partials in the backward, so splits cost only a gz re-read from L2:
-    // take many (best at the 256-split cap, profiles/r01_tune_bwd_*.jsonl)
-    const int64_t waves_target = 262144;
-    auto rps_of = [&](int k) { return (R + k - 1) / k; };
-    while (n < 256 && (n * wps < waves_target || rps_of(n) * G > kMaxRbRays) && rps_of(2 * n) >= 4) n *= 2;
-    const int rps = rps_of(n);
-    if (rps * G > kMaxRbRays) return fail(AVR_E_CONFIG, "ray_reduce_bwd: too many rays per split");
+    const int rps = rb_rays_per_split(R, (int64_t)groups * B * (sh.threads / 64), kMaxGroupRays / G);
+    if (rps * G > kMaxGroupRays) return fail(AVR_E_CONFIG, "ray_reduce_bwd: too many rays per split");
     const int64_t total = (int64_t)B * R * S * T;
-    const dim3 grid((R + rps - 1) / rps, groups, B);
+    const dim3 grid((R + rps - 1) / rps, groups, B), block(sh.threads);
     const size_t lds = (size_t)3 * G * max(rps, 1) * 4;
-    // streaming grad_x stores (NTS = true: profiles/r01_tune_bwd_*.jsonl), the
-    // launch bound by the block size
-#define AVR_RB(C, GG)                                                                              \
-    if (cpt == C && G == GG) {                                                                     \
-        auto kern = threads <= 512 ? ray_reduce_bwd_kernel<Tin, VECTOR, C, GG, 512, true>          \
-                                   : ray_reduce_bwd_kernel<Tin, VECTOR, C, GG, 1024, true>;        \
-        return launch("avr_ray_reduce_bwd", kern, grid, dim3(threads), lds, st, *p, (const Tin*)sig, gz, w, \
-                      delay, (Tin*)gsig, gw, B, R, S, T, rps, total);                              \
-    }
-    AVR_RB(1, 1) AVR_RB(1, 2) AVR_RB(1, 4) AVR_RB(2, 1) AVR_RB(2, 2) AVR_RB(2, 4) AVR_RB(3, 1)
-    AVR_RB(4, 1)
-#undef AVR_RB
-    return fail(AVR_E_CONFIG, "ray_reduce_bwd: T too long for this build");
-}
-
-// the aligned (16-byte vector) or the element-wise form of one signal dtype
-template <typename Tin>
-int launch_rb_any(const avr_render_params* p, int B, const void* sig, const float* gz, const float* w,
-                  const int32_t* delay, void* gsig, float* gw, hipStream_t st) {
-    const int64_t row = (int64_t)p->n_samples * p->T;
-    if (reinterpret_cast<uintptr_t>(sig) % 16 == 0 && reinterpret_cast<uintptr_t>(gsig) % 16 == 0 &&
-        row % Vec16<Tin>::N == 0)
-        return launch_rb<Tin, true>(p, B, sig, gz, w, delay, gsig, gw, st);
-    return launch_rb<Tin, false>(p, B, sig, gz, w, delay, gsig, gw, st);
+    auto go = [&](auto g, auto maxcpt) {
+        return dispatch_stream<maxcpt()>(sh.cpt, sh.threads, "ray_reduce_bwd", [&](auto cpt, auto maxt) {
+            return launch("avr_ray_reduce_bwd", ray_reduce_bwd_kernel<Tin, VECTOR, cpt(), g(), maxt()>, grid, block,
+                          lds, st, *p, (const Tin*)sig, gz, w, delay, (Tin*)gsig, gw, B, R, S, T, rps, total);
+        });
+    };
+    using std::integral_constant;
+    // a G > 1 super-row has one chunk per lane (dispatch_stream)
+    if (G == 4) return go(integral_constant<int, 4>{}, integral_constant<int, 1>{});
+    if (G == 2) return go(integral_constant<int, 2>{}, integral_constant<int, 1>{});
+    return go(integral_constant<int, 1>{}, integral_constant<int, kStreamMaxCpt<Tin, VECTOR>>{});
 }
 }  // namespace
 
@@ -619,90 +600,49 @@ extern "C" int avr_ray_reduce_bwd(const avr_render_params* p, int32_t B, const v
     AVR_REQUIRE(p && B >= 1 && signal && gz && w && delay && grad_signal && grad_w,
                 "avr_ray_reduce_bwd: bad args");
     AVR_REQUIRE(p->T >= 2 && p->T <= 16384, "avr_ray_reduce_bwd: T out of range");
+    const int64_t row = (int64_t)p->n_samples * p->T;
     return dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16, AVR_DTYPE_BF16>(
         sig_dtype, "avr_ray_reduce_bwd", [&](auto tag) {
-            return launch_rb_any<typename decltype(tag)::type>(p, B, signal, gz, w, delay, grad_signal, grad_w,
-                                                              as_stream(stream));
+            using Tin = typename decltype(tag)::type;
+            if (vector_ok<Tin>(row, signal, grad_signal))
+                return launch_rb<Tin, true>(p, B, signal, gz, w, delay, grad_signal, grad_w, as_stream(stream));
+            return launch_rb<Tin, false>(p, B, signal, gz, w, delay, grad_signal, grad_w, as_stream(stream));
         });
 }
 
 namespace {
-constexpr int mc_block(int left) { return left >= 4 ? 4 : left >= 2 ? 2 : 1; }
-
-struct McBwdShape {
-    int cpt, threads, rps;
-};
-
-// Chunks per lane, block size and rays per split (a split's slab of
-// (12 + 4*CB) bytes per ray within the 64 KiB a launch gets unasked) of the
-// multi-channel backward; one sample per column group.
-template <int VEC>
-int mc_bwd_shape(const avr_render_params* p, int B, int cb, McBwdShape* sh) {
-    const int R = n_rays(*p), S = p->n_samples, T = p->T;
-    int max_phase = 0;
-    for (int s0 = 0; s0 < S && s0 < VEC; ++s0) max_phase = max(max_phase, (int)(((int64_t)s0 * T) % VEC));
-    const int nch = (T + max_phase + VEC - 1) / VEC;
-    sh->cpt = 1;
-    while ((nch + sh->cpt - 1) / sh->cpt > kMaxRbThreads) ++sh->cpt;
-    if (sh->cpt > 4) return fail(AVR_E_CONFIG, "ray_reduce_bwd: T too long for this build");
-    sh->threads = max(64, ((nch + sh->cpt - 1) / sh->cpt + 63) / 64 * 64);
-    const int max_rays = min(kMaxRbRays, (int)(kLdsDefault / (12 + 4 * cb)));
-    // as launch_rb: many splits, at least 4 rays each
-    const int64_t wps = (int64_t)S * B * (sh->threads / 64);
-    auto rps_of = [&](int k) { return (R + k - 1) / k; };
-    int n = 1;
-    while (n < 256 && (n * wps < 262144 || rps_of(n) > max_rays) && rps_of(2 * n) >= 4) n *= 2;
-    sh->rps = rps_of(n);
-    if (sh->rps > max_rays) return fail(AVR_E_CONFIG, "ray_reduce_bwd: too many rays per split");
-    return 0;
-}
-
-template <typename Tin, bool VECTOR, int CB, bool ACCUM>
-int launch_rb_mc(const avr_render_params* p, int B, int C, int c0, const McBwdShape& sh, const void* sig,
-                 const float* gz, const float* w, const int32_t* delay, const float* gain, int64_t gstride,
-                 void* gsig, float* gw, hipStream_t st) {
-    const int R = n_rays(*p), S = p->n_samples, T = p->T;
-    const int64_t total = (int64_t)B * R * S * T;
-    const dim3 grid((R + sh.rps - 1) / sh.rps, S, B);
-    const size_t lds = (size_t)max(sh.rps, 1) * (12 + 4 * CB);
-    auto go = [&](auto c_tag) {
-        constexpr int CPT = decltype(c_tag)::value;
-        auto kern = sh.threads <= 512 ? ray_reduce_mc_bwd_kernel<Tin, VECTOR, CPT, CB, 512, ACCUM>
-                                      : ray_reduce_mc_bwd_kernel<Tin, VECTOR, CPT, CB, 1024, ACCUM>;
-        return launch("avr_ray_reduce_mc_bwd", kern, grid, dim3(sh.threads), lds, st, *p, (const Tin*)sig, gz, w,
-                      delay, gain, gstride, C, c0, (Tin*)gsig, gw, B, R, S, T, sh.rps, total);
-    };
-    switch (sh.cpt) {
-        case 1: return go(std::integral_constant<int, 1>{});
-        case 2: return go(std::integral_constant<int, 2>{});
-        case 3: return go(std::integral_constant<int, 3>{});
-        default: return go(std::integral_constant<int, 4>{});
-    }
-}
-
-// blocks of 4, then 2, then 1 channels; the first writes, the others add
+// blocks of 4, then 2, then 1 channels; the first writes, the others add.
+// One shape for the call: one sample per column group, the rays per split by
+// the slab of the widest block, (12 + 4*CB) bytes per ray within the 64 KiB a
+// launch gets unasked.
 template <typename Tin, bool VECTOR>
 int launch_rb_mc_blocks(const avr_render_params* p, int B, int C, const void* sig, const float* gz, const float* w,
                         const int32_t* delay, const float* gain, int64_t gstride, void* gsig, float* gw,
                         hipStream_t st) {
     constexpr int VEC = VECTOR ? Vec16<Tin>::N : 1;
-    McBwdShape sh;
-    if (int e = mc_bwd_shape<VEC>(p, B, mc_block(C), &sh)) return e;
+    const int R = n_rays(*p), S = p->n_samples, T = p->T;
+    const StreamShape sh = stream_shape<VEC>(S, T, 1);
+    const int max_rays = min(kMaxGroupRays, (int)(kLdsDefault / (12 + 4 * mc_block(C))));
+    const int rps = rb_rays_per_split(R, (int64_t)S * B * (sh.threads / 64), max_rays);
+    if (rps > max_rays) return fail(AVR_E_CONFIG, "ray_reduce_bwd: too many rays per split");
+    const int64_t total = (int64_t)B * R * S * T;
+    const dim3 grid((R + rps - 1) / rps, S, B), block(sh.threads);
     for (int c0 = 0; c0 < C;) {
         const int cb = mc_block(C - c0);
-        int e;
-#define AVR_RB_MC(CB)                                                                                          \
-    e = c0 == 0 ? launch_rb_mc<Tin, VECTOR, CB, false>(p, B, C, c0, sh, sig, gz, w, delay, gain, gstride, gsig, \
-                                                        gw, st)                                                \
-                : launch_rb_mc<Tin, VECTOR, CB, true>(p, B, C, c0, sh, sig, gz, w, delay, gain, gstride, gsig,  \
-                                                       gw, st)
-        if (cb == 4)
-            AVR_RB_MC(4);
-        else if (cb == 2)
-            AVR_RB_MC(2);
-        else
-            AVR_RB_MC(1);
-#undef AVR_RB_MC
+        auto go = [&](auto CB, auto accum) {
+            const size_t lds = (size_t)max(rps, 1) * (12 + 4 * CB());
+            return dispatch_stream<kStreamMaxCpt<Tin, VECTOR>>(
+                sh.cpt, sh.threads, "ray_reduce_bwd", [&](auto cpt, auto maxt) {
+                    return launch("avr_ray_reduce_mc_bwd",
+                                  ray_reduce_mc_bwd_kernel<Tin, VECTOR, cpt(), CB(), maxt(), accum()>, grid, block, lds,
+                                  st, *p, (const Tin*)sig, gz, w, delay, gain, gstride, C, c0, (Tin*)gsig, gw, B, R, S,
+                                  T, rps, total);
+                });
+        };
+        auto first_or_add = [&](auto CB) { return c0 == 0 ? go(CB, std::false_type{}) : go(CB, std::true_type{}); };
+        const int e = cb == 4   ? first_or_add(std::integral_constant<int, 4>{})
+                      : cb == 2 ? first_or_add(std::integral_constant<int, 2>{})
+                                : first_or_add(std::integral_constant<int, 1>{});
         if (e) return e;
         c0 += cb;
     }
@@ -716,7 +656,7 @@ extern "C" int avr_ray_reduce_mc_bwd(const avr_render_params* p, int32_t B, int3
                                      void* stream) {
     AVR_REQUIRE(p && B >= 1 && signal && gz && w && delay && gain && grad_signal && grad_w,
                 "avr_ray_reduce_mc_bwd: bad args");
-    AVR_REQUIRE(C >= 1 && C <= 16, "avr_ray_reduce_mc_bwd: C must be 1..16");
+    AVR_REQUIRE(C >= 1 && C <= kMaxChannels, "avr_ray_reduce_mc_bwd: C must be 1..16");
     AVR_REQUIRE(p->T >= 2 && p->T <= 16384, "avr_ray_reduce_mc_bwd: T out of range");
     AVR_REQUIRE(gain_b_stride == 0 || gain_b_stride == (int64_t)C * n_rays(*p),
                 "avr_ray_reduce_mc_bwd: gain_b_stride must be 0 ([C,R]) or C*R ([B,C,R])");
@@ -724,8 +664,7 @@ extern "C" int avr_ray_reduce_mc_bwd(const avr_render_params* p, int32_t B, int3
     return dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16, AVR_DTYPE_BF16>(
         sig_dtype, "avr_ray_reduce_mc_bwd", [&](auto tag) {
             using Tin = typename decltype(tag)::type;
-            if (reinterpret_cast<uintptr_t>(signal) % 16 == 0 && reinterpret_cast<uintptr_t>(grad_signal) % 16 == 0 &&
-                row % Vec16<Tin>::N == 0)
+            if (vector_ok<Tin>(row, signal, grad_signal))
                 return launch_rb_mc_blocks<Tin, true>(p, B, C, signal, gz, w, delay, gain, gain_b_stride,
                                                       grad_signal, grad_w, as_stream(stream));
             return launch_rb_mc_blocks<Tin, false>(p, B, C, signal, gz, w, delay, gain, gain_b_stride, grad_signal,

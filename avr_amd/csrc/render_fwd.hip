@@ -7,6 +7,7 @@
 // reordering (sum over rays in the time domain before the transform) and the
 // roofline of each kernel.
 #include "common.h"
+#include "ray_stream.h"
 
 #include <cstdlib>
 
@@ -315,8 +316,6 @@ __global__ __launch_bounds__(256) void weights_fwd_kernel(
 // has the same alignment phase, so a lane's register accumulators always see
 // the same t indices.  The per-ray w/delay of the split are gathered into
 // LDS once.
-constexpr int kMaxReduceThreads = 1024;
-constexpr int kMaxGroupRays = 4096;  // G * rays_per_split (LDS: 32 KiB of w/delay)
 
 // One workgroup per (ray split, column group, b).  A column group is G
 // consecutive samples s0..s0+G-1 whose rows are contiguous in memory for
@@ -1048,88 +1047,68 @@ extern "C" int avr_weights_fwd(const avr_render_params* p, int32_t B, const void
 }
 
 namespace {
-// Rows in flight per lane of the streaming reduction (non-temporal loads):
-// the best of the sweeps (profiles/r01_tune*; 8 rows was slower).
-constexpr int kReduceRows = 4;
-
-struct ReduceShape {
-    int G, cpt, threads;
-};
-
-// Column group, chunks per lane and block size for one (T, VEC, S).
-template <int VEC>
-ReduceShape reduce_shape(int S, int T) {
-    ReduceShape sh;
-    // one sample per column group: G = 1 beat G = 2 (and G = 2 beat G = 4)
-    // on configs 2 (fp32 and fp16) and 3 in every interleaved round of the
-    // round-2 sweeps (profiles/r02_sweepG_*.jsonl: config 2 fp32 111.8 vs
-    // 115.7 us per launch); fewer w/delay selects per loaded element
-    sh.G = 1;
-    int max_phase = 0;  // group starts are s0 = multiples of G; S*T % VEC == 0
-    for (int s0 = 0; s0 < S && s0 < VEC * sh.G; s0 += sh.G)
-        max_phase = max(max_phase, (int)(((int64_t)s0 * T) % VEC));
-    const int nch = (sh.G * T + max_phase + VEC - 1) / VEC;
-    sh.cpt = 1;
-    while ((nch + sh.cpt - 1) / sh.cpt > kMaxReduceThreads) ++sh.cpt;
-    const int need = (nch + sh.cpt - 1) / sh.cpt;
-    sh.threads = max(64, (need + 63) / 64 * 64);
-    return sh;
-}
-
-template <typename Tin, bool VECTOR>
-int launch_reduce(const avr_render_params* p, int B, const void* sig, const float* w,
-                  const int32_t* delay, int n_split, float* part, hipStream_t st) {
+// Channels c0..c0+CB-1 of a C-channel reduction, or (GAIN false: C = 1) the
+// ungained one; `what` names the entry point in errors.
+template <typename Tin, bool VECTOR, int CB, bool GAIN>
+int launch_reduce(const char* what, const avr_render_params* p, int B, int C, int c0, const void* sig,
+                  const float* w, const int32_t* delay, const float* gain, int64_t gstride, int n_split,
+                  float* part, hipStream_t st) {
     constexpr int VEC = VECTOR ? Vec16<Tin>::N : 1;
     const int R = n_rays(*p), S = p->n_samples, T = p->T;
     const int rps = (R + n_split - 1) / n_split;
-    const ReduceShape sh = reduce_shape<VEC>(S, T);
-    if (sh.G * rps > kMaxGroupRays)
-        return fail(AVR_E_ARG, "avr_ray_reduce_fwd: too many rays per split (raise n_split)");
+    // one sample per column group: G = 1 beat G = 2 and 4 in the round-2 sweeps
+    // 
+    const StreamShape sh = stream_shape<VEC>(S, T, 1);
     const int64_t total = (int64_t)B * R * S * T;
-    const dim3 grid(n_split, (S + sh.G - 1) / sh.G, B);
-    const dim3 block(sh.threads);
-    const size_t lds = (size_t)sh.G * max(rps, 1) * 8;
-    // chunks per lane (template) x launch bound (512 threads leave 256 VGPRs
-    // per lane, 1024 only 128); reduce_shape() gives G = 1 and cpt <= 4
-    auto go = [&](auto c_tag) {
-        constexpr int C = decltype(c_tag)::value;
-        auto kern = block.x <= 512 ? ray_reduce_fwd_kernel<Tin, VECTOR, C, kReduceRows, 1, 512>
-                                   : ray_reduce_fwd_kernel<Tin, VECTOR, C, kReduceRows, 1, 1024>;
-        return launch("avr_ray_reduce_fwd", kern, grid, block, lds, st, *p, (const Tin*)sig, w, delay, part, B, R, S,
-                      T, rps, total);
-    };
-    if (sh.G == 1) switch (sh.cpt) {
-            case 1: return go(std::integral_constant<int, 1>{});
-            case 2: return go(std::integral_constant<int, 2>{});
-            case 3: return go(std::integral_constant<int, 3>{});
-            case 4: return go(std::integral_constant<int, 4>{});
-        }
-    return fail(AVR_E_CONFIG, "ray_reduce: T too long for this build");
+    const dim3 grid(n_split, S, B), block(sh.threads);
+    const size_t lds = (size_t)max(rps, 1) * (4 + 4 * CB);
+    return dispatch_stream<kStreamMaxCpt<Tin, VECTOR>>(sh.cpt, sh.threads, what, [&](auto cpt, auto maxt) {
+        if constexpr (GAIN)
+            return launch(what, ray_reduce_mc_fwd_kernel<Tin, VECTOR, cpt(), kReduceRows, CB, maxt()>, grid, block, lds, st, *p,
+                          (const Tin*)sig, w, delay, gain, gstride, C, c0, part, B, R, S, T, rps, total);
+        else
+            return launch(what, ray_reduce_fwd_kernel<Tin, VECTOR, cpt(), kReduceRows, 1, maxt()>, grid, block, lds, st, *p,
+                          (const Tin*)sig, w, delay, part, B, R, S, T, rps, total);
+    });
 }
 
-// the aligned (16-byte vector) or the element-wise form of one signal dtype
-template <typename Tin>
-int launch_reduce_any(const avr_render_params* p, int B, const void* sig, const float* w, const int32_t* delay,
-                      int n_split, float* part, hipStream_t st) {
-    const int64_t row = (int64_t)p->n_samples * p->T;
-    if (reinterpret_cast<uintptr_t>(sig) % 16 == 0 && row % Vec16<Tin>::N == 0)
-        return launch_reduce<Tin, true>(p, B, sig, w, delay, n_split, part, st);
-    return launch_reduce<Tin, false>(p, B, sig, w, delay, n_split, part, st);
+// all C channels in blocks of 4, then 2, then 1
+template <typename Tin, bool VECTOR>
+int launch_reduce_mc_blocks(const avr_render_params* p, int B, int C, const void* sig, const float* w,
+                            const int32_t* delay, const float* gain, int64_t gstride, int n_split, float* part,
+                            hipStream_t st) {
+    for (int c0 = 0; c0 < C;) {
+        const int cb = mc_block(C - c0);
+        auto go = [&](auto CB) {
+            return launch_reduce<Tin, VECTOR, CB(), true>("avr_ray_reduce_mc_fwd", p, B, C, c0, sig, w, delay, gain,
+                                                           gstride, n_split, part, st);
+        };
+        const int e = cb == 4   ? go(std::integral_constant<int, 4>{})
+                      : cb == 2 ? go(std::integral_constant<int, 2>{})
+                                : go(std::integral_constant<int, 1>{});
+        if (e) return e;
+        c0 += cb;
+    }
+    return 0;
 }
-}  // namespace
 
-namespace {
+// Rays per split of a C-channel call: the slab of its widest channel block,
+// (4 + 4*CB) bytes per ray, stays within the 64 KiB a launch gets unasked.
+constexpr int mc_max_rays(int C) {
+    const int fit = (int)(kLdsDefault / (4 + 4 * mc_block(C)));
+    return fit < kMaxGroupRays ? fit : kMaxGroupRays;
+}
+
 // The split rule of the ray reduction for `max_rays` rays per split at most
 // (the LDS slab of the kernel that will run).
 int choose_reduce_splits(const avr_render_params* p, int B, int sig_dtype, int max_rays, int32_t* n_split) {
     const int R = n_rays(*p), S = p->n_samples, T = p->T;
     const int vec = (sig_dtype == AVR_DTYPE_F16 || sig_dtype == AVR_DTYPE_BF16) ? 8 : 4;
-    const ReduceShape sh = vec == 8 ? reduce_shape<8>(S, T) : reduce_shape<4>(S, T);
-    const int groups = (S + sh.G - 1) / sh.G;
+    const StreamShape sh = vec == 8 ? stream_shape<8>(S, T, 1) : stream_shape<4>(S, T, 1);
     auto rps = [&](int k) { return (R + k - 1) / k; };
     if (const char* f = getenv("AVR_NSPLIT")) {  // validated tuning knob: 1, 2, 4, 8 or 16 ray splits
         const int v = atoi(f);
-        if ((v == 1 || v == 2 || v == 4 || v == 8 || v == 16) && v <= R && rps(v) * sh.G <= max_rays) {
+        if ((v == 1 || v == 2 || v == 4 || v == 8 || v == 16) && v <= R && rps(v) <= max_rays) {
             *n_split = v;
             return 0;
         }
@@ -1139,12 +1118,10 @@ int choose_reduce_splits(const avr_render_params* p, int B, int sig_dtype, int m
     // a split's w/delay within the 32 KiB LDS slab.  Sweeps:
     // profiles/r01_sweep_*.jsonl.
     const int64_t waves_target = (vec == 8) ? 4096 : 1536;
-    const int64_t waves_per_split = (int64_t)groups * B * (sh.threads / 64);
+    const int64_t waves_per_split = (int64_t)S * B * (sh.threads / 64);
     int n = 1;
-    while (n < 16 && (n * waves_per_split < waves_target || rps(n) * sh.G > max_rays) &&
-           rps(2 * n) >= 8)
-        n *= 2;
-    if (rps(n) * sh.G > max_rays) return fail(AVR_E_CONFIG, "avr_reduce_splits: too many rays");
+    while (n < 16 && (n * waves_per_split < waves_target || rps(n) > max_rays) && rps(2 * n) >= 8) n *= 2;
+    if (rps(n) > max_rays) return fail(AVR_E_CONFIG, "avr_reduce_splits: too many rays");
     *n_split = n;
     return 0;
 }
@@ -1166,73 +1143,20 @@ extern "C" int avr_ray_reduce_fwd(const avr_render_params* p, int32_t B, const v
     AVR_REQUIRE(n_split >= 1 && n_split <= R, "avr_ray_reduce_fwd: n_split out of range");
     AVR_REQUIRE((R + n_split - 1) / n_split <= kMaxGroupRays,
                 "avr_ray_reduce_fwd: too many rays per split (raise n_split)");
+    const int64_t row = (int64_t)p->n_samples * p->T;
     return dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16, AVR_DTYPE_BF16>(
         sig_dtype, "avr_ray_reduce_fwd", [&](auto tag) {
-            return launch_reduce_any<typename decltype(tag)::type>(p, B, signal, w, delay, n_split, part,
-                                                                  as_stream(stream));
+            using Tin = typename decltype(tag)::type;
+            auto go = [&](auto vector) {
+                // one channel, no gain: C = 1, c0 = 0, gain = nullptr, gain stride 0
+                return launch_reduce<Tin, vector(), 1, false>("avr_ray_reduce_fwd", p, B, 1, 0, signal, w, delay, nullptr,
+                                                              0, n_split, part, as_stream(stream));
+            };
+            return vector_ok<Tin>(row, signal) ? go(std::true_type{}) : go(std::false_type{});
         });
 }
 
 // ---- C receiver channels: per-ray gains on the ray sum, one stream per block
-namespace {
-constexpr int kMaxChannels = 16;
-constexpr int mc_block(int left) { return left >= 4 ? 4 : left >= 2 ? 2 : 1; }
-// Rays per split of a C-channel call: the slab of its widest channel block,
-// (4 + 4*CB) bytes per ray, stays within the 64 KiB a launch gets unasked.
-constexpr int mc_max_rays(int C) {
-    const int fit = (int)(kLdsDefault / (4 + 4 * mc_block(C)));
-    return fit < kMaxGroupRays ? fit : kMaxGroupRays;
-}
-
-template <typename Tin, bool VECTOR, int CB>
-int launch_reduce_mc(const avr_render_params* p, int B, int C, int c0, const void* sig, const float* w,
-                     const int32_t* delay, const float* gain, int64_t gstride, int n_split, float* part,
-                     hipStream_t st) {
-    constexpr int VEC = VECTOR ? Vec16<Tin>::N : 1;
-    const int R = n_rays(*p), S = p->n_samples, T = p->T;
-    const int rps = (R + n_split - 1) / n_split;
-    const ReduceShape sh = reduce_shape<VEC>(S, T);
-    const int64_t total = (int64_t)B * R * S * T;
-    const dim3 grid(n_split, S, B);
-    const dim3 block(sh.threads);
-    const size_t lds = (size_t)max(rps, 1) * (4 + 4 * CB);
-    auto go = [&](auto c_tag) {
-        constexpr int CPT = decltype(c_tag)::value;
-        auto kern = block.x <= 512 ? ray_reduce_mc_fwd_kernel<Tin, VECTOR, CPT, kReduceRows, CB, 512>
-                                   : ray_reduce_mc_fwd_kernel<Tin, VECTOR, CPT, kReduceRows, CB, 1024>;
-        return launch("avr_ray_reduce_mc_fwd", kern, grid, block, lds, st, *p, (const Tin*)sig, w, delay, gain,
-                      gstride, C, c0, part, B, R, S, T, rps, total);
-    };
-    switch (sh.cpt) {
-        case 1: return go(std::integral_constant<int, 1>{});
-        case 2: return go(std::integral_constant<int, 2>{});
-        case 3: return go(std::integral_constant<int, 3>{});
-        case 4: return go(std::integral_constant<int, 4>{});
-    }
-    return fail(AVR_E_CONFIG, "ray_reduce: T too long for this build");
-}
-
-// all C channels in blocks of 4, then 2, then 1
-template <typename Tin, bool VECTOR>
-int launch_reduce_mc_blocks(const avr_render_params* p, int B, int C, const void* sig, const float* w,
-                            const int32_t* delay, const float* gain, int64_t gstride, int n_split, float* part,
-                            hipStream_t st) {
-    for (int c0 = 0; c0 < C;) {
-        const int cb = mc_block(C - c0);
-        int e;
-        if (cb == 4)
-            e = launch_reduce_mc<Tin, VECTOR, 4>(p, B, C, c0, sig, w, delay, gain, gstride, n_split, part, st);
-        else if (cb == 2)
-            e = launch_reduce_mc<Tin, VECTOR, 2>(p, B, C, c0, sig, w, delay, gain, gstride, n_split, part, st);
-        else
-            e = launch_reduce_mc<Tin, VECTOR, 1>(p, B, C, c0, sig, w, delay, gain, gstride, n_split, part, st);
-        if (e) return e;
-        c0 += cb;
-    }
-    return 0;
-}
-}  // namespace
-
 extern "C" int avr_reduce_mc_splits(const avr_render_params* p, int32_t B, int32_t C, int32_t sig_dtype,
                                     int32_t* n_split, int32_t* max_rays) {
     if (int e = validate(p)) return e;
@@ -1259,7 +1183,7 @@ extern "C" int avr_ray_reduce_mc_fwd(const avr_render_params* p, int32_t B, int3
     return dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16, AVR_DTYPE_BF16>(
         sig_dtype, "avr_ray_reduce_mc_fwd", [&](auto tag) {
             using Tin = typename decltype(tag)::type;
-            if (reinterpret_cast<uintptr_t>(signal) % 16 == 0 && row % Vec16<Tin>::N == 0)
+            if (vector_ok<Tin>(row, signal))
                 return launch_reduce_mc_blocks<Tin, true>(p, B, C, signal, w, delay, gain, gain_b_stride, n_split,
                                                           part, as_stream(stream));
             return launch_reduce_mc_blocks<Tin, false>(p, B, C, signal, w, delay, gain, gain_b_stride, n_split,

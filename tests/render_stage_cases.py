@@ -71,6 +71,13 @@ class ReduceCase:
 
 _F32_VEC = [(2, 2046), (2, 2050), (2, 4098), (2, 8194), (2, 12290), (2, 16384)]
 _H_VEC = [(4, 8190), (4, 8194), (4, 16382)]
+# both sides of every chunks-per-lane boundary of the vector path (1024 lanes
+# of 4 or 8 elements): the launchers instantiate only the (chunks per lane,
+# launch bound) pairs a shape can reach, and these shapes reach each of them
+CPT_EDGES = (
+    [ReduceCase(2, T, "float32", n_splits=(1, 4)) for T in (4096, 4100, 8192, 8196, 12288, 12292)]
+    + [ReduceCase(4, T, d, n_splits=(1, 4)) for d in ("float16", "bfloat16") for T in (8192, 8200)]
+)
 
 # (a) forward, vector path: 512 / 1024 threads, 1-4 chunks per lane, column
 # phases 0/2 (fp32) and 0/6/4/2 (16-bit); R = 7 with 1, 2, 4 splits (4-ray
@@ -79,6 +86,7 @@ REDUCE_FWD_VECTOR = (
     [ReduceCase(S, T, "float32") for S, T in _F32_VEC]
     + [ReduceCase(S, T, d) for d in ("float16", "bfloat16") for S, T in _H_VEC]
     + [ReduceCase(2, 2050, "float32", R=5, n_splits=(4,)), ReduceCase(4, 8194, "float16", R=5, n_splits=(4,))]
+    + CPT_EDGES
 )
 # (b) scalar path: S*T not a multiple of the vector width (1-4 chunks per
 # lane), and one vector shape with the tensor one element off alignment
@@ -95,6 +103,7 @@ REDUCE_BWD_VECTOR = (
     [ReduceCase(S, T, "float32") for S, T in _F32_VEC]
     + [ReduceCase(S, T, d) for d in ("float16", "bfloat16") for S, T in _H_VEC]
     + [ReduceCase(5, 254, "float32"), ReduceCase(5, 510, "float32"), ReduceCase(3, 1022, "float32")]
+    + CPT_EDGES
 )
 ALL_REDUCE = REDUCE_FWD_VECTOR + REDUCE_SCALAR + REDUCE_BWD_VECTOR + [SCALAR_LIMIT]
 

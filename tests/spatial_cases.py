@@ -38,8 +38,10 @@ MC_FWD = (
     + [ReduceCase(3, 510, "float32", vector=False), ReduceCase(3, 1026, "bfloat16", vector=False),
        ReduceCase(2, 2050, "float32", vector=False, offset=1)]
 )
+_MC_BASE = len(MC_FWD)
+MC_FWD = MC_FWD + list(rsc.CPT_EDGES)  # both sides of every chunks-per-lane boundary, splits (1, 4)
 MC_FWD = MC_FWD + [ReduceCase(c.S, c.T, c.dtype, R=5, n_splits=(4,), vector=c.vector, offset=c.offset)
-                   for c in MC_FWD]
+                   for c in MC_FWD[:_MC_BASE]]
 # backward: the same shapes (R = 7; it picks its own splits) plus two short rows
 MC_BWD = [c for c in MC_FWD if c.R == 7] + [ReduceCase(5, 254, "float32"), ReduceCase(3, 1022, "float32")]
 
