@@ -22,12 +22,16 @@ from .metrics import (  # noqa: F401
 )
 from .auralize import (  # noqa: F401
     auralize_dump,
+    auralize_path,
     butter_bandpass_sos,
     convolve_source,
+    convolve_trajectory,
     seg_hop_samples,
     sliding_frames,
     sosfilt_zi,
     synth_observation,
+    synth_trajectory,
+    trajectory_weights,
     white_noise,
     zero_phase_sos,
 )

@@ -186,6 +186,7 @@ _SIGS = {
     "avr_group_bias_relu_bwd": (ctypes.c_int, [_c_i64, _c_i32, _c_i64, _c_i32, _vp, _vp, _c_i32, _vp, _vp, _vp,
                                                _c_i64, _vp, _vp]),
     "avr_conv_source": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, _c_i64, _vp, _vp, _vp, _vp]),
+    "avr_conv_trajectory": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp]),
     "avr_sosfiltfilt_workspace": (ctypes.c_int, [_c_i64, _c_i64, _c_i32, _c_i32, _vp]),
     "avr_sosfiltfilt": (ctypes.c_int, [_c_i64, _c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _c_i32, _vp, _c_i32,
                                        _vp, _c_i64, _vp]),

@@ -8,6 +8,12 @@ whitenoise_long_doa.py:95-104).
     L, H = seg_hop_samples(fs, seg_ms, overlap)
     frames = sliding_frames(y, L, H)                  # [..., n_frames, L], a view
 
+Beyond the reference, a source or listener that moves:
+
+    y = convolve_trajectory(ir, x, hop, fade)         # ir [P, C, Nh] at P path points
+    y = synth_trajectory(spec, x, hop, fade)          # from spectra [P, C, F]
+    y = auralize_path(renderer, rays_o, position_tx, x, hop)  # from P poses
+
 `convolve_source` is one GEMM with a Toeplitz operand on the exact-fp32 MFMA
 (`csrc/auralize.hip`, C-ABI `avr_conv_source`); `zero_phase_sos` runs scipy's
 direct-form-II-transposed recurrence in fp64, one thread per row
@@ -96,6 +102,151 @@ def synth_observation(spec, x):
     with torch.no_grad():
         ir = spectrum_to_ir(spec.detach())
     return convolve_source(ir, x)
+
+
+# ---------------------------------------------------------------- trajectory
+
+def _hop_fade(name, hop, fade):
+    if isinstance(hop, bool) or not isinstance(hop, (int, np.integer)) or hop < 1:
+        raise ValueError(f"{name}: hop must be an integer >= 1, got {hop!r}")
+    fade = hop if fade is None else fade
+    if isinstance(fade, bool) or not isinstance(fade, (int, np.integer)) or not 0 <= fade <= hop:
+        raise ValueError(f"{name}: fade must be an integer in [0, hop = {hop}], got {fade!r}")
+    if fade >= 1 << 23:
+        raise ValueError(f"{name}: fade must be below 2^23, got {fade}")
+    return int(hop), int(fade)
+
+
+def trajectory_weights(P, L, hop, fade):
+    """The weights of `convolve_trajectory` on the host, for tests and plots:
+    w [P, L] float32, w[p, m] the share of source sample m played through path
+    point p.  With q = min(m // hop, P-1) and j = m - ((q+1) hop - fade): in
+    the crossfade at the end of interval q (q+1 < P, j >= 0)
+    u = fp32(2j+1) / fp32(2 fade), w[q+1, m] = u, w[q, m] = fp32(1 - u);
+    elsewhere w[q, m] = 1.  The last point holds to the end."""
+    if P < 1 or L < 1:
+        raise ValueError(f"trajectory_weights: P and L must be positive, got {P} and {L}")
+    hop, fade = _hop_fade("trajectory_weights", hop, fade)
+    m = np.arange(L, dtype=np.int64)
+    q = np.minimum(m // hop, P - 1)
+    j = m - ((q + 1) * hop - fade)
+    cross = (q + 1 < P) & (j >= 0)
+    mc, qc = m[cross], q[cross]
+    u = (2 * j[cross] + 1).astype(np.float32) / np.float32(2 * fade) if mc.size else np.zeros(0, np.float32)
+    w = np.zeros((P, L), np.float32)
+    w[q, m] = 1.0
+    w[qc, mc] = np.float32(1.0) - u
+    w[qc + 1, mc] = u
+    return w
+
+
+def convolve_trajectory(ir, x, hop, fade=None):
+    """The source `x` [L] heard along a path: `ir` [P, C, Nh] holds the impulse
+    responses at P path points, one point every `hop` source samples, and
+    every source sample is played through the IR in force when it is emitted
+    (a moving source; to first order a slowly moving listener), crossfading
+    linearly to the next point over the last `fade` samples of each hop
+    (`trajectory_weights`; fade=None means hop: linear interpolation of the
+    IRs along the path; 0 switches hard).  The last point holds to the end of
+    `x`.  Returns [C, L+Nh-1] fp32, or [L+Nh-1] for `ir` [P, Nh].
+
+    One launch on the exact-fp32 MFMA (C-ABI `avr_conv_trajectory`), a fixed
+    summation order: bitwise repeatable, a row does not depend on the other
+    channels, and P = 1, or fade = 0 with equal IRs, gives
+    `convolve_source(ir[0], x)` bitwise."""
+    _need_hip(ir, "ir")
+    _need_hip(x, "x")
+    if ir.dim() not in (2, 3) or x.dim() != 1:
+        raise ValueError(f"convolve_trajectory: ir [P, C, Nh] or [P, Nh] and x [L] expected, got "
+                         f"{tuple(ir.shape)} and {tuple(x.shape)}")
+    if ir.device != x.device:
+        raise ValueError("convolve_trajectory: ir and x are on different devices")
+    hop, fade = _hop_fade("convolve_trajectory", hop, fade)
+    h = ir.detach().float().contiguous()
+    xs = x.detach().float().contiguous()
+    P, Nh = h.size(0), h.size(-1)
+    C = 1 if h.dim() == 2 else h.size(1)
+    L = xs.size(0)
+    if min(P, C, Nh, L) < 1:
+        raise ValueError("convolve_trajectory: empty input")
+    dev = h.device
+    y = torch.empty((C, L + Nh - 1), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("avr_conv_trajectory", P, C, Nh, L, hop, fade, _ptr(h), _ptr(xs), _ptr(y), _stream(dev))
+    return y[0] if ir.dim() == 2 else y
+
+
+def synth_trajectory(spec, x, hop, fade=None):
+    """`synth_observation` along a path: the irfft of the spectra `spec`
+    ([P, C, F] complex64 or [P, C, F, 2] float) at the P path points
+    (`spectrum_to_ir`) -> [P, C, 2(F-1)], then `convolve_trajectory`."""
+    from .renderer import spectrum_to_ir
+
+    _need_hip(spec, "spec")
+    if spec.is_complex():
+        spec = torch.view_as_real(spec.detach().to(torch.complex64))
+    if spec.dim() != 4 or spec.size(-1) != 2 or spec.size(2) < 2:
+        raise ValueError(f"synth_trajectory: spec [P, C, F] complex or [P, C, F, 2] with F >= 2 expected, "
+                         f"got {tuple(spec.shape)}")
+    P, C, F = spec.shape[:3]
+    with torch.no_grad():
+        ir = spectrum_to_ir(spec.detach().reshape(P * C, F, 2))
+    return convolve_trajectory(ir.view(P, C, -1), x, hop, fade)
+
+
+def auralize_path(renderer, rays_o, position_tx, x, hop, fade=None, direction_tx=None, ch_idx=None,
+                  ray_gain=None, pose_chunk=64):
+    """`x` heard while moving through the rendered field: the P poses
+    `rays_o` [P, 3] (listener) and `position_tx` [P, 3] or [3] (source;
+    `direction_tx` [P, 3] or [3] and `ch_idx` [P] or one value where the
+    network takes them) are rendered
+    with `renderer.render_ir` under `no_grad`, `pose_chunk` poses per call,
+    and `x` is convolved along them (`convolve_trajectory`).  Returns
+    [C, L+T-1]: C = 1 for the omnidirectional receiver, the channels of
+    `ray_gain` ([C, R] or a callable, see `AVRRender.forward`; a per-pose
+    gain [P, C, R] is cut with the poses) for a directional one.
+
+    The azimuth jitter is drawn once (`draw_jitter`, the CPU generator's two
+    draws of one render) and handed to every chunk: all points of the path
+    look at the same sphere of rays."""
+    from .renderer import draw_jitter
+
+    _need_hip(x, "x")
+    if rays_o.dim() != 2 or rays_o.size(-1) != 3 or rays_o.size(0) < 1:
+        raise ValueError(f"auralize_path: rays_o [P, 3] expected, got {tuple(rays_o.shape)}")
+    if pose_chunk < 1:
+        raise ValueError("auralize_path: pose_chunk must be positive")
+    hop, fade = _hop_fade("auralize_path", hop, fade)
+    P = rays_o.size(0)
+
+    def per_pose(t, name):
+        if t is None:
+            return None
+        if t.dim() == 1 and t.size(0) == 3:
+            return t.expand(P, 3)
+        if tuple(t.shape) != (P, 3):
+            raise ValueError(f"auralize_path: {name} [{P}, 3] or [3] expected, got {tuple(t.shape)}")
+        return t
+
+    position_tx = per_pose(position_tx, "position_tx")
+    direction_tx = per_pose(direction_tx, "direction_tx")
+    if ch_idx is not None:  # the network's channel of each pose; one value serves all
+        ch_idx = torch.as_tensor(ch_idx).reshape(-1)
+        if ch_idx.numel() not in (1, P):
+            raise ValueError(f"auralize_path: ch_idx needs 1 or {P} entries, got {ch_idx.numel()}")
+        ch_idx = ch_idx.expand(P)
+    per_pose_gain = isinstance(ray_gain, torch.Tensor) and ray_gain.dim() == 3
+    if per_pose_gain and ray_gain.size(0) != P:
+        raise ValueError(f"auralize_path: a per-pose ray_gain needs {P} poses, got {ray_gain.size(0)}")
+    u_azi = draw_jitter(renderer.n_azi, renderer.n_ele)
+    irs = []
+    with torch.no_grad():
+        for i in range(0, P, pose_chunk):
+            s = slice(i, i + pose_chunk)
+            _, ir = renderer.render_ir(rays_o[s], position_tx[s], None if direction_tx is None else direction_tx[s],
+                                       None if ch_idx is None else ch_idx[s], ray_gain=ray_gain[s] if per_pose_gain else ray_gain, u_azi=u_azi)
+            irs.append(ir.reshape(ir.size(0), -1, ir.size(-1)))
+    return convolve_trajectory(irs[0] if len(irs) == 1 else torch.cat(irs), x, hop, fade)
 
 
 # ------------------------------------------------------- zero-phase filter

@@ -7,7 +7,13 @@
 //   avr_sosfiltfilt   scipy.signal.sosfiltfilt(sos, y, axis=-1), fp64,
 //                     one thread per row
 //
-// DESIGN.md §18.
+// and, beyond the reference, a source or listener that moves:
+//
+//   avr_conv_trajectory  the same GEMM per path point, each source sample
+//                     played through the IR in force when it is emitted,
+//                     crossfaded linearly between points
+//
+// DESIGN.md §18, §22.
 #include "common.h"
 
 namespace avr {
@@ -180,6 +186,217 @@ __global__ __launch_bounds__(kConvThreads) void conv_source_kernel(
         for (int reg = 0; reg < kRegs; ++reg) {
             const int c = c0 + (R == 32 ? (reg & 3) + 8 * (reg >> 2) + 4 * kq : 4 * kq + reg);
             if (c < C) y[((int64_t)s * C + c) * N + n] = acc[t][reg];
+        }
+    }
+}
+
+// ------------------------------------------ time-varying source convolution
+// Y[c, n] = sum_p sum_k H[p, c, k] * xw[p, n - k], xw[p, m] = w[p, m] x[m]:
+// source sample m is played through the IR of the path point in force at
+// emission time m, with a linear crossfade over the last `fade` samples of
+// each hop.  conv_source_kernel's tiling, stages, fragment
+// ring and MFMAs; a stage runs once per path point whose support meets the
+// stage's window of x, the later point first: for one output the later point
+// holds the smaller taps, so the non-zero products stay in ascending tap
+// order, and a product with a zero xw leaves the fp32 FMA chain as it was.
+// With one point, or with fade = 0 and equal IRs, the chain is
+// conv_source_kernel's.
+struct TrajArgs {
+    int32_t P, C, Nh;
+    int64_t L, N, hop, fade;
+};
+
+// point p sounds over source samples [traj_first(p), traj_end(p)); the last
+// point holds to the end of x
+__device__ __forceinline__ int64_t traj_first(const TrajArgs& a, int p) {
+    return p > 0 ? (int64_t)p * a.hop - a.fade : 0;
+}
+__device__ __forceinline__ int64_t traj_end(const TrajArgs& a, int p) {
+    return p + 1 < a.P ? ((int64_t)p + 1) * a.hop : a.L;
+}
+// w[p, m] for m in [0, L): u = fp32(2j + 1) / fp32(2 fade), one correctly
+// rounded division (2j + 1 < 2^24 is exact), fading in over the `fade`
+// samples before p's interval and out as 1 - u over the last `fade` of it
+__device__ __forceinline__ float traj_weight(const TrajArgs& a, int p, int64_t m) {
+    const int64_t lo = (int64_t)p * a.hop;
+    const float den = (float)(2 * a.fade);
+    if (p > 0 && m < lo) {
+        const int64_t j = m - (lo - a.fade);
+        return j >= 0 ? __fdiv_rn((float)(2 * j + 1), den) : 0.0f;
+    }
+    if (p + 1 < a.P) {
+        const int64_t j = m - (lo + a.hop - a.fade);
+        if (m >= lo + a.hop) return 0.0f;
+        if (j >= 0) return 1.0f - __fdiv_rn((float)(2 * j + 1), den);
+    }
+    return 1.0f;
+}
+
+template <int R>
+__global__ __launch_bounds__(kConvThreads) void conv_trajectory_kernel(
+    TrajArgs a, const float* __restrict__ h, const float* __restrict__ x, float* __restrict__ y) {
+    using Acc = std::conditional_t<R == 32, floatx16, floatx4>;
+    constexpr int kRegs = R == 32 ? 16 : 4;
+    constexpr int kTiles = kConvWave / R;
+    constexpr int kSteps = kConvFrag / kTiles;
+    constexpr int kPer = 4 / kSteps;
+    __shared__ float As[kConvKc][R + 1];
+    __shared__ float xs[kConvWin];
+    const int C = a.C, Nh = a.Nh;
+    const int64_t L = a.L, N = a.N;
+    const int64_t nb = (int64_t)blockIdx.x * kConvNB;
+    const int c0 = blockIdx.y * R;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int kq = lane / R, j = lane % R;
+
+    // the stages of conv_source_kernel
+    const int64_t klo = nb - (L - 1);
+    const int k_begin = klo > 0 ? (int)(klo / kConvKc) * kConvKc : 0;
+    const int k_end = (int)(nb + kConvNB < (int64_t)Nh ? nb + kConvNB : (int64_t)Nh);
+
+    // A stage's window of x is [nb - k0 - (Kc-1), nb - k0 + NB - 1] cut to
+    // [0, L); the points that sound in it are p_lo .. p_hi.  The window moves
+    // down by Kc per stage, so both only ever step down: no division per stage.
+    auto win_lo = [&](int k0) {
+        const int64_t g = nb - k0 - (kConvKc - 1);
+        return g > 0 ? g : (int64_t)0;
+    };
+    auto win_hi = [&](int k0) {
+        const int64_t g = nb - k0 + (kConvNB - 1);
+        return g < L ? g : L - 1;
+    };
+    int p_lo = 0, p_hi = 0;
+    if (k_begin < k_end) {
+        const int64_t last = a.P - 1;
+        const int64_t ql = win_lo(k_begin) / a.hop, qh = (win_hi(k_begin) + a.fade) / a.hop;
+        p_lo = (int)(ql < last ? ql : last);
+        p_hi = (int)(qh < last ? qh : last);
+    }
+    auto settle = [&](int k0) {
+        const int64_t lo = win_lo(k0), hi = win_hi(k0);
+        while (p_hi > 0 && traj_first(a, p_hi) > hi) --p_hi;
+        while (p_lo > 0 && traj_end(a, p_lo - 1) > lo) --p_lo;
+    };
+
+    constexpr int kARows = R / 4;
+    const int col = threadIdx.x & 63, row0 = threadIdx.x >> 6;
+    float araw[kARows], xraw[kConvXLoads];
+    auto issue = [&](int k0, int p) {
+        const int k = k0 + col;
+        const int kc = k < Nh ? k : Nh - 1;
+#pragma unroll
+        for (int i = 0; i < kARows; ++i) {
+            const int c = c0 + row0 + 4 * i;
+            const int cc = c < C ? c : C - 1;
+            araw[i] = h[((int64_t)p * C + cc) * Nh + kc];
+        }
+        // xs[i] = xw[p, nb - k0 - (Kc-1) + i]: the weight goes on here, once
+        const int64_t xbase = nb - k0 - (kConvKc - 1);
+#pragma unroll
+        for (int i = 0; i < kConvXLoads; ++i) {
+            int64_t g = xbase + i * kConvThreads + (int)threadIdx.x;
+            const bool ok = g >= 0 && g < L;
+            g = g < 0 ? 0 : (g < L ? g : L - 1);
+            const float v = traj_weight(a, p, g) * x[g];
+            xraw[i] = ok ? v : 0.0f;
+        }
+    };
+    auto commit = [&](int k0) {
+        const bool kok = k0 + col < Nh;
+#pragma unroll
+        for (int i = 0; i < kARows; ++i) {
+            const bool ok = kok && (c0 + row0 + 4 * i) < C;
+            As[col][row0 + 4 * i] = ok ? araw[i] : 0.0f;
+        }
+#pragma unroll
+        for (int i = 0; i < kConvXLoads; ++i) {
+            const int w = i * kConvThreads + (int)threadIdx.x;
+            if (w < kConvWin) xs[w] = xraw[i];
+        }
+    };
+
+    Acc acc[kTiles];
+#pragma unroll
+    for (int t = 0; t < kTiles; ++t)
+#pragma unroll
+        for (int i = 0; i < kRegs; ++i) acc[t][i] = 0.0f;
+
+    const int bbase = wave * kConvWave + j - kq + (kConvKc - 1);
+    float aq[3][kSteps], bq[3][kConvFrag];
+    auto fetch = [&](int g, float* af, float* bf) {
+#pragma unroll
+        for (int p = 0; p < kSteps; ++p) {
+            const int kk = 4 * g + kPer * p;
+            af[p] = As[kk + kq][j];
+#pragma unroll
+            for (int t = 0; t < kTiles; ++t) bf[p * kTiles + t] = xs[bbase + t * R - kk];
+        }
+#pragma unroll
+        for (int i = 0; i < kConvFrag; ++i) asm volatile("" : "+v"(bf[i]));
+#pragma unroll
+        for (int p = 0; p < kSteps; ++p) asm volatile("" : "+v"(af[p]));
+    };
+    auto hold = [&](const float* af, const float* bf) {
+#pragma unroll
+        for (int i = 0; i < kConvFrag; ++i) keep_live(bf[i]);
+#pragma unroll
+        for (int p = 0; p < kSteps; ++p) keep_live(af[p]);
+    };
+
+    // the (stage, point) pairs in order: stages ascending, points descending
+    int k0 = k_begin, p = 0;
+    bool more = k_begin < k_end;
+    if (more) {
+        settle(k0);
+        p = p_hi;
+        issue(k0, p);
+    }
+    while (more) {
+        int k0n = k0, pn = p - 1;
+        if (pn < p_lo) {
+            k0n = k0 + kConvKc;
+            more = k0n < k_end;
+            if (more) {
+                settle(k0n);
+                pn = p_hi;
+            }
+        }
+        __syncthreads();
+        commit(k0);
+        __syncthreads();
+        if (more) issue(k0n, pn);  // the next pair's loads fly under the MFMAs
+        // a wave whose own 128 outputs meet none of p's samples in this stage
+        // would add +0 products only
+        const int64_t wlo = nb + wave * kConvWave - k0 - (kConvKc - 1);
+        if (traj_first(a, p) <= wlo + (kConvWave + kConvKc - 2) && traj_end(a, p) > wlo) {
+            // the fragment ring of conv_source_kernel
+            fetch(0, aq[0], bq[0]);
+#pragma unroll
+            for (int g = 0; g < kConvGroups; ++g) {
+                if (g + 1 < kConvGroups) fetch(g + 1, aq[(g + 1) % 3], bq[(g + 1) % 3]);
+#pragma unroll
+                for (int s = 0; s < kSteps; ++s)
+#pragma unroll
+                    for (int t = 0; t < kTiles; ++t)
+                        acc[t] = conv_mfma<R>(aq[g % 3][s], bq[g % 3][s * kTiles + t], acc[t]);
+                __builtin_amdgcn_sched_barrier(0);
+                if (g >= 1) hold(aq[(g - 1) % 3], bq[(g - 1) % 3]);
+            }
+            mfma_queue_wait();
+            hold(aq[(kConvGroups - 1) % 3], bq[(kConvGroups - 1) % 3]);
+            hold(aq[(kConvGroups - 2) % 3], bq[(kConvGroups - 2) % 3]);
+        }
+        k0 = k0n;
+        p = pn;
+    }
+#pragma unroll
+    for (int t = 0; t < kTiles; ++t) {
+        const int64_t n = nb + wave * kConvWave + t * R + j;
+        if (n >= N) continue;
+#pragma unroll
+        for (int reg = 0; reg < kRegs; ++reg) {
+            const int c = c0 + (R == 32 ? (reg & 3) + 8 * (reg >> 2) + 4 * kq : 4 * kq + reg);
+            if (c < C) y[((int64_t)c) * N + n] = acc[t][reg];
         }
     }
 }
@@ -368,6 +585,28 @@ extern "C" int avr_conv_source(int32_t S, int32_t C, int32_t Nh, int64_t L, cons
     const dim3 grid((unsigned)nblk, (unsigned)ctiles, (unsigned)S);
     return launch("conv_source_kernel", R == 16 ? conv_source_kernel<16> : conv_source_kernel<32>, grid,
                   dim3(kConvThreads), 0, as_stream(stream), C, Nh, L, N, h, x, y);
+}
+
+extern "C" int avr_conv_trajectory(int32_t P, int32_t C, int32_t Nh, int64_t L, int64_t hop, int64_t fade,
+                                   const float* h, const float* x, float* y, void* stream) {
+    AVR_REQUIRE(P >= 1 && C >= 1 && Nh >= 1 && L >= 1 && hop >= 1,
+                "avr_conv_trajectory: P, C, Nh, L and hop must be positive");
+    AVR_REQUIRE(fade >= 0 && fade <= hop, "avr_conv_trajectory: 0 <= fade <= hop required");
+    AVR_REQUIRE(fade < ((int64_t)1 << 23), "avr_conv_trajectory: fade must be below 2^23");
+    AVR_REQUIRE(h && x && y, "avr_conv_trajectory: null pointer");
+    AVR_REQUIRE(L <= ((int64_t)1 << 40), "avr_conv_trajectory: source too long");
+    const int64_t N = L + Nh - 1;
+    const int64_t nblk = (N + kConvNB - 1) / kConvNB;
+    const int R = C <= 16 ? 16 : 32;
+    const int64_t ctiles = ((int64_t)C + R - 1) / R;
+    AVR_REQUIRE(nblk <= 0x7fffffffLL, "avr_conv_trajectory: output too long");
+    AVR_REQUIRE(ctiles <= 65535, "avr_conv_trajectory: at most 65535 * 32 channels");
+    // x ends before point 0 starts to fade: point 0 alone, at weight 1.  Any
+    // other hop is below L + 2^23, so the kernel's p * hop stays far inside 64 bits.
+    TrajArgs a{hop - fade >= L ? 1 : P, C, Nh, L, N, hop, fade};
+    const dim3 grid((unsigned)nblk, (unsigned)ctiles);
+    return launch("conv_trajectory_kernel", R == 16 ? conv_trajectory_kernel<16> : conv_trajectory_kernel<32>,
+                  grid, dim3(kConvThreads), 0, as_stream(stream), a, h, x, y);
 }
 
 extern "C" int avr_sosfiltfilt_workspace(int64_t rows, int64_t n, int32_t n_sections, int32_t padlen,

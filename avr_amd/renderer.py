@@ -12,6 +12,9 @@ Mirrors `renderer.py` of the reference (KMASAHIRO/AVR):
 * keyword-only `ray_gain` on `forward` / `render_ir` (not in the reference):
   a directional receiver as per-ray gains, output [B, C, F, 2]
   (`RenderCoreMC`, `avr_amd.spatial`).
+* keyword-only `u_azi` on `forward` / `render_ir` (not in the reference): a
+  `draw_jitter` result in place of the call's own draw, so the poses of a
+  path see one sphere of rays (`avr_amd.auralize.auralize_path`).
 * module functions `ray_directions`, `normalize_points`,
   `denormalize_points` with the reference's names (renderer.py:127-165).
 
@@ -838,8 +841,12 @@ class AVRRender(nn.Module):
                 out = _poison_nonfinite(out, (attn, h, weight))
             return out
 
-    def forward(self, rays_o, position_tx, direction_tx=None, ch_idx=None, *, ray_gain=None):
+    def forward(self, rays_o, position_tx, direction_tx=None, ch_idx=None, *, ray_gain=None, u_azi=None):
         """Render [B, F, 2] (real, imag) spectra; see renderer.py:31-124.
+
+        `u_azi` [n_azi] (a `draw_jitter` result, host or device) replaces this
+        call's draw of the azimuth jitter from the CPU generator, so that
+        several calls look at one sphere of rays; None draws as before.
 
         `ray_gain`: a directional receiver, the per-ray gains g[c, r] on the
         ray sum (avr_amd.spatial builds the usual patterns) as a tensor [R],
@@ -847,20 +854,21 @@ class AVRRender(nn.Module):
         the device with this call's jittered directions.  The output is then
         [B, C, F, 2] ([B, F, 2] for a 1-D gain); None renders the
         omnidirectional receiver as before."""
-        return self._render(rays_o, position_tx, direction_tx, ch_idx, None, ray_gain=ray_gain)
+        return self._render(rays_o, position_tx, direction_tx, ch_idx, None, u_azi=u_azi, ray_gain=ray_gain)
 
-    def render_ir(self, rays_o, position_tx, direction_tx=None, ch_idx=None, *, ray_gain=None):
+    def render_ir(self, rays_o, position_tx, direction_tx=None, ch_idx=None, *, ray_gain=None, u_azi=None):
         """(spectrum [B, F, 2], IR [B, 2(F-1)]): forward plus
         `torch.real(torch.fft.irfft(...))` (utils/criterion.py:71).  Without
         autograd the IR is computed in the same native call; with autograd
         recording it is spectrum_to_ir(out), which differentiates.  With
         `ray_gain` (see forward) both carry the channel axis: [B, C, F, 2]
-        and [B, C, 2(F-1)]."""
+        and [B, C, 2(F-1)].  `u_azi`: see forward."""
         ir = []
         # the IR inside the render's native call is a forward-only side
         # output; with autograd recording, take it differentiably instead
         grad = torch.is_grad_enabled()
-        out = self._render(rays_o, position_tx, direction_tx, ch_idx, None if grad else ir, ray_gain=ray_gain)
+        out = self._render(rays_o, position_tx, direction_tx, ch_idx, None if grad else ir, u_azi=u_azi,
+                           ray_gain=ray_gain)
         if ir:
             return out, ir[0]
         if out.dim() == 4:

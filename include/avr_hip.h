@@ -705,11 +705,27 @@ int avr_group_bias_relu_bwd(int64_t N, int32_t W, int64_t rows_per_group, int32_
  *   form II transposed in fp64, one thread per row.  The workspace holds
  *   avr_sosfiltfilt_workspace bytes (the forward pass over the extended rows).
  *
+ * avr_conv_trajectory (not in the reference): a source or
+ *   listener moving along P path points with IRs h [P][C][Nh], one point every
+ *   `hop` samples of x [L].  Source sample m is played through the IR in force
+ *   when it is emitted: with q = min(m / hop, P-1) and j = m - ((q+1) hop - fade),
+ *   the last `fade` samples of interval q (q+1 < P, j >= 0) crossfade linearly,
+ *   u = fp32(2j+1) / fp32(2 fade), w[q+1][m] = u, w[q][m] = fp32(1 - u); every
+ *   other sample has w[q][m] = 1, and the last point holds to the end of x.
+ *   y [C][L + Nh - 1]: y[c][n] = sum_p sum_k h[p][c][k] * fp32(w[p][m] x[m]),
+ *   m = n - k, fp32 on the exact-fp32 MFMA in a fixed order, one launch, the
+ *   weights computed in the kernel.  The result repeats bitwise, a channel's
+ *   row does not depend on the other channels, and P = 1, or fade = 0 with P
+ *   equal IRs, gives avr_conv_source's bits.  hop >= 1, 0 <= fade <= hop,
+ *   fade < 2^23, L <= 2^40; element offsets are 64-bit.
+ *
  * No call synchronises or copies to the host.  Bad arguments are refused
  * (AVR_E_ARG) before any device call. */
 #define AVR_DTYPE_F64 3
 int avr_conv_source(int32_t S, int32_t C, int32_t Nh, int64_t L, const float* h, const float* x,
                     float* y, void* stream);
+int avr_conv_trajectory(int32_t P, int32_t C, int32_t Nh, int64_t L, int64_t hop, int64_t fade,
+                        const float* h, const float* x, float* y, void* stream);
 int avr_sosfiltfilt_workspace(int64_t rows, int64_t n, int32_t n_sections, int32_t padlen,
                               int64_t* bytes);
 int avr_sosfiltfilt(int64_t rows, int64_t n, int32_t n_sections, int32_t padlen, const double* sos,

@@ -15,6 +15,14 @@ own functions on the machine that wrote the fixtures); they are per channel
 and per core and are not multiplied out here.
 
     python tools/bench_auralize.py --out profiles/auralize_gpu.json
+
+`--trajectory` times `convolve_trajectory` instead (C = 8 and 144, the same
+three Nh, 8 s, a path point every 100 ms, fade = hop and hop / 4) with
+`convolve_source` at the same C, Nh and L, measured in the same run, as the
+yardstick; the issued count follows the kernel's own (stage, point, wave)
+passes.
+
+    python tools/bench_auralize.py --trajectory   # profiles/auralize_trajectory_gpu.json
 """
 from __future__ import annotations
 
@@ -62,13 +70,82 @@ def issued_flop(C, Nh, L):
     return total * rows * ((C + rows - 1) // rows)
 
 
+def issued_flop_trajectory(P, C, Nh, L, hop, fade):
+    """What conv_trajectory_kernel's MFMAs execute: per output block and
+    64-tap stage, one pass per path point whose samples meet the stage's
+    window of x, in each wave (128 outputs) whose own window meets them."""
+    N = L + Nh - 1
+    first = lambda p: p * hop - fade if p > 0 else 0          # noqa: E731
+    end = lambda p: (p + 1) * hop if p + 1 < P else L          # noqa: E731
+    if hop - fade >= L:
+        P = 1
+    passes = 0
+    for blk in range((N + 511) // 512):
+        nb = blk * 512
+        k_begin = max(0, (nb - (L - 1)) // 64 * 64)
+        k_end = min(Nh, nb + 512)
+        for k0 in range(k_begin, k_end, 64):
+            lo, hi = max(nb - k0 - 63, 0), min(nb - k0 + 511, L - 1)
+            for p in range(min(lo // hop, P - 1), min((hi + fade) // hop, P - 1) + 1):
+                for wave in range(4):
+                    wlo = nb + 128 * wave - k0 - 63
+                    passes += first(p) <= wlo + 190 and end(p) > wlo
+    rows = 16 if C <= 16 else 32
+    return passes * 64 * 128 * 2 * rows * ((C + rows - 1) // rows)
+
+
+def trajectory(args):
+    """`convolve_trajectory` against `convolve_source` (the static kernel, the
+    yardstick) at the same C, Nh and L in the same run: 8 s at 16 kHz, a path
+    point every 100 ms, crossfades over the whole hop and over a quarter."""
+    from avr_amd import auralize
+
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(0)
+    L, hop = 8 * FS, 1600
+    P = (L + hop - 1) // hop
+    res = dict(device=torch.cuda.get_device_name(0), peak_tf=PEAK_TF, fs=FS, seconds=8, hop=hop, points=P, rows=[])
+    x = torch.from_numpy(rng.standard_normal(L).astype(np.float32)).to(dev)
+    for C in (8, 144):
+        for Nh in (1022, 1600, 4094):
+            h = torch.from_numpy(rng.standard_normal((P, C, Nh)).astype(np.float32)).to(dev)
+            h0 = h[0].contiguous()
+            static, *_ = _time(lambda: auralize.convolve_source(h0, x), 10, 5)
+            static_issued = float(issued_flop(C, Nh, L))
+            for fade in (hop, hop // 4):
+                med, lo, hi = _time(lambda: auralize.convolve_trajectory(h, x, hop, fade), 10, 5)
+                issued = float(issued_flop_trajectory(P, C, Nh, L, hop, fade))
+                row = dict(C=C, Nh=Nh, L=L, hop=hop, fade=fade, ms=round(med, 4), ms_min=round(lo, 4),
+                           ms_max=round(hi, 4), issued_tflops=round(issued / med / 1e9, 2),
+                           issued_of_peak=round(issued / med / 1e9 / PEAK_TF, 4),
+                           static_ms=round(static, 4), static_issued_tflops=round(static_issued / static / 1e9, 2),
+                           ratio_to_static=round(med / static, 3), issued_ratio=round(issued / static_issued, 3),
+                           expected_ratio=round(1 + fade / hop, 3))
+                res["rows"].append(row)
+                print(json.dumps(row), flush=True)
+            del h, h0
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "auralize_gpu.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/auralize_gpu.json, or "
+                    "profiles/auralize_trajectory_gpu.json with --trajectory")
     ap.add_argument("--quick", action="store_true", help="8 s sources only")
+    ap.add_argument("--trajectory", action="store_true",
+                    help="time convolve_trajectory against convolve_source instead (DESIGN.md §22)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles",
+                                "auralize_trajectory_gpu.json" if args.trajectory else "auralize_gpu.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_auralize: no HIP device (nothing is measured on the CPU)")
+    if args.trajectory:
+        return trajectory(args)
     from avr_amd import auralize
 
     dev = torch.device("cuda", 0)
