@@ -114,10 +114,21 @@ __device__ __forceinline__ void store_pair<__half>(__half* out, int64_t i, float
 
 // avr_hashgrid_fwd switches to the level-major dispatch from this many points
 constexpr int64_t kLevelMajorMinPoints = 16384;
-inline int64_t lm_min_points() { return kLevelMajorMinPoints; }
 
-// grouped corner loads in the level-major forward (fp16 tables, §9b)
-inline bool group_loads() { return true; }
+// One level as the kernels read it: its table (of `params` or of the
+// gradient), entry count, grid resolution and coordinate scale.
+template <typename T>
+struct Level {
+    float scale;
+    uint32_t size, res;
+    T* table;
+};
+// (the members in the order the kernels read them: with the table first the
+// forward and bias kernels compiled to other address arithmetic)
+template <typename T>
+__device__ __forceinline__ Level<T> level_view(const LevelTable& lt, int l, T* params) {
+    return {lt.scale[l], (uint32_t)(lt.offset[l + 1] - lt.offset[l]), lt.res[l], params + 2 * lt.offset[l]};
+}
 
 struct Corner {
     float pos[3];
@@ -136,6 +147,40 @@ __device__ __forceinline__ Corner locate(const float* x, float scale) {
     return c;
 }
 
+// Corner k of a located cell (x bit fastest): its trilinear weight and table
+// entry.  The one place that holds tcnn's order of multiplications (d = 0, 1,
+// 2 from 1.0f), on which parity depends; every kernel below calls it.
+__device__ __forceinline__ void corner(const Corner& c, int k, uint32_t size, uint32_t res, float& w, uint32_t& e) {
+    w = 1.0f;
+    uint32_t g[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        if (k & (1 << d)) {
+            w *= c.pos[d];
+            g[d] = c.grid[d] + 1;
+        } else {
+            w *= 1.0f - c.pos[d];
+            g[d] = c.grid[d];
+        }
+    }
+    e = grid_index(size, res, g[0], g[1], g[2]);
+}
+
+// The feature pair of point xi at one level: the corner sum in index order
+template <typename Tp>
+__device__ __forceinline__ float2 encode_point_level(const float* xi, const Level<const Tp>& lv) {
+    const Corner c = locate(xi, lv.scale);
+    CornerAcc<Tp> acc;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        float w;
+        uint32_t e;
+        corner(c, k, lv.size, lv.res, w, e);
+        acc.add(w, CornerAcc<Tp>::load(lv.table, e));
+    }
+    return acc.get();
+}
+
 template <typename Tp, typename To>
 __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(int64_t N, int L,
                                                            const float* __restrict__ x,
@@ -146,26 +191,18 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(int64_t N, int L,
     const int64_t i = q / L;
     const int l = (int)(q % L);
     const float xi[3] = {x[i * 3 + 0], x[i * 3 + 1], x[i * 3 + 2]};
-    const Corner c = locate(xi, lt.scale[l]);
-    const uint32_t size = (uint32_t)(lt.offset[l + 1] - lt.offset[l]);
-    const uint32_t res = lt.res[l];
-    const Tp* table = params + 2 * lt.offset[l];
+    // encode_point_level's body, kept here: called, it compiles to packed
+    // arithmetic and two more VGPRs, and measured slower than the parent's
+    // spread at 16383 points in one of two sessions
+    const Level<const Tp> lv = level_view(lt, l, params);
+    const Corner c = locate(xi, lv.scale);
     CornerAcc<Tp> acc;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        float wgt = 1.0f;
-        uint32_t g[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            if (k & (1 << d)) {
-                wgt *= c.pos[d];
-                g[d] = c.grid[d] + 1;
-            } else {
-                wgt *= 1.0f - c.pos[d];
-                g[d] = c.grid[d];
-            }
-        }
-        acc.add(wgt, CornerAcc<Tp>::load(table, grid_index(size, res, g[0], g[1], g[2])));
+        float w;
+        uint32_t e;
+        corner(c, k, lv.size, lv.res, w, e);
+        acc.add(w, CornerAcc<Tp>::load(lv.table, e));
     }
     store_pair(out, q, acc.get());
 }
@@ -226,31 +263,15 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_lm_kernel(int64_t N, const f
 #pragma unroll
         for (int d = 0; d < 3; ++d) xi[d] = 0.5f + 0.5f * xi[d];
     }
-    const Corner c = locate(xi, lt.scale[l]);
-    const uint32_t size = (uint32_t)(lt.offset[l + 1] - lt.offset[l]);
-    const uint32_t res = lt.res[l];
-    const Tp* table = params + 2 * lt.offset[l];
+    const Level<const Tp> lv = level_view(lt, l, params);
+    const Tp* table = lv.table;
+    const Corner c = locate(xi, lv.scale);
     CornerAcc<Tp> acc;
     // corner weights and entries in the order k = 0..7 (x bit fastest)
     float wgt[8];
     uint32_t ent[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        float w = 1.0f;
-        uint32_t g[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            if (k & (1 << d)) {
-                w *= c.pos[d];
-                g[d] = c.grid[d] + 1;
-            } else {
-                w *= 1.0f - c.pos[d];
-                g[d] = c.grid[d];
-            }
-        }
-        wgt[k] = w;
-        ent[k] = grid_index(size, res, g[0], g[1], g[2]);
-    }
+    for (int k = 0; k < 8; ++k) corner(c, k, lv.size, lv.res, wgt[k], ent[k]);
     if constexpr (GROUP) {
         constexpr uint32_t kN = EntryGroup<Tp>::kN;
         EntryGroup<Tp> grp[4];
@@ -309,10 +330,8 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(int64_t N, int L, int
     const int slot = threadIdx.x & 15;
     const int k = slot >> 1, f = slot & 1;
     const int64_t first = ((int64_t)blockIdx.x * 16 + (threadIdx.x >> 4)) * RUN;
-    const uint32_t size = (uint32_t)(lt.offset[l + 1] - lt.offset[l]);
-    const uint32_t res = lt.res[l];
-    const float scale = lt.scale[l];
-    float* __restrict__ table = gparams + 2 * lt.offset[l];
+    const Level<float> lv = level_view(lt, l, gparams);
+    float* __restrict__ table = lv.table;
     float xi[RUN][3], g[RUN];
 #pragma unroll
     for (int it = 0; it < RUN; ++it) {
@@ -326,20 +345,10 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(int64_t N, int L, int
     float pv = 0.0f;
 #pragma unroll
     for (int it = 0; it < RUN; ++it) {
-        const Corner c = locate(xi[it], scale);
-        float wgt = 1.0f;
-        uint32_t gg[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            if (k & (1 << d)) {
-                wgt *= c.pos[d];
-                gg[d] = c.grid[d] + 1;
-            } else {
-                wgt *= 1.0f - c.pos[d];
-                gg[d] = c.grid[d];
-            }
-        }
-        const uint32_t e = 2u * grid_index(size, res, gg[0], gg[1], gg[2]) + (uint32_t)f;
+        float wgt;
+        uint32_t ce;
+        corner(locate(xi[it], lv.scale), k, lv.size, lv.res, wgt, ce);
+        const uint32_t e = 2u * ce + (uint32_t)f;
         const float v = wgt * g[it];
         if (e == pe) {
             pv += v;
@@ -395,7 +404,7 @@ int make_table(int L, const int64_t* off, const float* scale, const int32_t* res
 template <bool ROW_MAJOR>
 int launch_fwd_lm(const char* what, dim3 grid, hipStream_t st, int64_t N, const float* x, const void* params,
                   int32_t param_dtype, const LevelTable& lt, void* out, int32_t out_dtype, int unit = 0) {
-    const bool grp = group_loads() && ((uintptr_t)params & 15) == 0;
+    const bool grp = ((uintptr_t)params & 15) == 0;
     return dispatch_fwd_dtypes(param_dtype, out_dtype, what, [&](auto pt, auto ot) {
         using Tp = typename decltype(pt)::type;
         using To = typename decltype(ot)::type;
@@ -447,23 +456,12 @@ struct BwdPlan {
 };
 
 // One point's contribution to corner k (the walk's arithmetic): the entry
-// and the value pair w_k * g.
-__device__ __forceinline__ void corner_value(const float (&xi)[3], float g0, float g1, int k, float scale,
-                                             uint32_t size, uint32_t res, uint32_t& e, float& v0, float& v1) {
-    const Corner c = locate(xi, scale);
-    float wgt = 1.0f;
-    uint32_t gg[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        if (k & (1 << d)) {
-            wgt *= c.pos[d];
-            gg[d] = c.grid[d] + 1;
-        } else {
-            wgt *= 1.0f - c.pos[d];
-            gg[d] = c.grid[d];
-        }
-    }
-    e = grid_index(size, res, gg[0], gg[1], gg[2]);
+// and the value pair w_k * g.  (A function of its own: written out in
+// bwd_walk the same operations compile to fewer packed instructions.)
+__device__ __forceinline__ void corner_value(const float (&xi)[3], float g0, float g1, int k,
+                                             const Level<const float>& lv, uint32_t& e, float& v0, float& v1) {
+    float wgt;
+    corner(locate(xi, lv.scale), k, lv.size, lv.res, wgt, e);
     v0 = wgt * g0;
     v1 = wgt * g1;
 }
@@ -513,9 +511,7 @@ __device__ __forceinline__ void bwd_walk(int64_t N, int L, int l, const float* _
                                          const Tg* __restrict__ gout, const LevelTable& lt, Emit&& emit) {
     const int k = threadIdx.x & 7;
     const int64_t first = ((int64_t)blockIdx.x * kBwdGroups + (threadIdx.x >> 3)) * kBwdRun;
-    const uint32_t size = (uint32_t)(lt.offset[l + 1] - lt.offset[l]);
-    const uint32_t res = lt.res[l];
-    const float scale = lt.scale[l];
+    const Level<const float> lv = level_view<const float>(lt, l, nullptr);  // (the walk reads no table)
     float xi[kBwdRun][3], g0[kBwdRun], g1[kBwdRun];
 #pragma unroll
     for (int it = 0; it < kBwdRun; ++it) point_inputs(first + it, N, L, l, x, gout, xi[it], g0[it], g1[it]);
@@ -525,7 +521,7 @@ __device__ __forceinline__ void bwd_walk(int64_t N, int L, int l, const float* _
     for (int it = 0; it < kBwdRun; ++it) {
         uint32_t e;
         float v0, v1;
-        corner_value(xi[it], g0[it], g1[it], k, scale, size, res, e, v0, v1);
+        corner_value(xi[it], g0[it], g1[it], k, lv, e, v0, v1);
         if (e == pe) {
             p0 += v0;
             p1 += v1;
@@ -555,6 +551,18 @@ __global__ __launch_bounds__(256) void hg_bwd_count_kernel(int64_t N, int L, con
         counts[(int64_t)(plan.pbase[l] + p) * plan.nchunks + blockIdx.x] = cnt_l[p];
 }
 
+// Inclusive scan of v over the wave's 64 lanes (the integer scans of the
+// scan, plan and scatter passes; 1-D blocks, so the lane is threadIdx.x & 63)
+__device__ __forceinline__ int wave_scan_incl(int v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int o = __shfl_up(v, off, 64);
+        if (lane >= off) v += o;
+    }
+    return v;
+}
+
 // one wave per partition: per-chunk counts -> exclusive offsets within the
 // partition (in place), and the partition's total
 __global__ __launch_bounds__(1024) void hg_bwd_scan_kernel(int total_parts, int nchunks, int* __restrict__ counts,
@@ -566,12 +574,7 @@ __global__ __launch_bounds__(1024) void hg_bwd_scan_kernel(int total_parts, int 
     int carry = 0;
     for (int c0 = 0; c0 < nchunks; c0 += 64) {
         const int v = c0 + lane < nchunks ? c[c0 + lane] : 0;
-        int incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int o = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += o;
-        }
+        const int incl = wave_scan_incl(v);
         if (c0 + lane < nchunks) c[c0 + lane] = carry + incl - v;
         carry += __shfl(incl, 63, 64);
     }
@@ -638,15 +641,7 @@ __global__ __launch_bounds__(1024) void hg_bwd_plan_kernel(int total_parts, BwdP
             ss += slices(tv[u], l);
         }
     }
-    int it = st, is = ss;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int ut = __shfl_up(it, off, 64), us = __shfl_up(is, off, 64);
-        if (lane >= off) {
-            it += ut;
-            is += us;
-        }
-    }
+    const int it = wave_scan_incl(st), is = wave_scan_incl(ss);
     if (lane == 63) {
         ws_t[wave] = it;
         ws_s[wave] = is;
@@ -727,12 +722,7 @@ __global__ __launch_bounds__(256) void hg_bwd_scatter_kernel(int64_t N, int L, c
         lofs[q] = c;  // (the count, until the scan below)
         run += c;
     }
-    int incl = run;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int u = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += u;
-    }
+    const int incl = wave_scan_incl(run);
     if (lane == 63) wsum[wave] = incl;
     __syncthreads();
     int acc = incl - run;
@@ -779,6 +769,20 @@ __device__ __forceinline__ float wave_total(float x) {
            (__int_as_float(__builtin_amdgcn_readlane(xi, 32)) + __int_as_float(__builtin_amdgcn_readlane(xi, 48)));
 }
 
+// Partition p's entries in the gradient: how many, and where its 2 * ne
+// floats start.  Level sizes are multiples of 8 entries: ne is, and the
+// partition's floats start 16-byte aligned (the float4 accesses below).
+struct PartSpan {
+    int ne;
+    float* dst;
+};
+__device__ __forceinline__ PartSpan part_span(const LevelTable& lt, const BwdPlan& plan, int p, float* gparams) {
+    int l = 0;
+    while (plan.pbase[l + 1] <= p) ++l;
+    const int64_t e0 = (int64_t)(p - plan.pbase[l]) * kPartEntries;
+    return {(int)min((int64_t)kPartEntries, lt.offset[l + 1] - lt.offset[l] - e0), gparams + 2 * (lt.offset[l] + e0)};
+}
+
 // One wave per partition slice, with the partition's image in the wave's own
 // LDS (no other wave touches it).  LDS float atomics measured slow on this
 // path (the reduce pass took ~160 of 330 us with ds_add_f32), so each
@@ -810,13 +814,9 @@ __global__ __launch_bounds__(64 * kReduceWaves) void hg_bwd_reduce_kernel(LevelT
     const int p = lo;
     const int ns = slice_base[p + 1] - slice_base[p], sl = b - slice_base[p];
     const int n = totals[p];
-    int l = 0;
-    while (plan.pbase[l + 1] <= p) ++l;
-    const int64_t e0 = (int64_t)(p - plan.pbase[l]) * kPartEntries;
-    // level sizes are multiples of 8 entries: ne is, and the partition's
-    // 2*ne floats start 16-byte aligned
-    const int ne = (int)min((int64_t)kPartEntries, lt.offset[l + 1] - lt.offset[l] - e0);
-    float* dstf = gparams + 2 * (lt.offset[l] + e0);
+    const PartSpan span = part_span(lt, plan, p, gparams);
+    const int ne = span.ne;
+    float* dstf = span.dst;
     if (n == 0) {  // wave-uniform
         if (overwrite) {  // (a partition without contributions has one slice)
             float4* dst = reinterpret_cast<float4*>(dstf);
@@ -916,12 +916,9 @@ __global__ __launch_bounds__(256) void hg_bwd_zero_hot_kernel(LevelTable lt, Bwd
                                                               float* __restrict__ gparams) {
     const int p = blockIdx.x;
     if (p >= total_parts || slice_base[p + 1] - slice_base[p] <= 1) return;
-    int l = 0;
-    while (plan.pbase[l + 1] <= p) ++l;
-    const int64_t e0 = (int64_t)(p - plan.pbase[l]) * kPartEntries;
-    const int ne = (int)min((int64_t)kPartEntries, lt.offset[l + 1] - lt.offset[l] - e0);
-    float4* dst = reinterpret_cast<float4*>(gparams + 2 * (lt.offset[l] + e0));
-    for (int i = threadIdx.x; i < ne / 2; i += 256) dst[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    const PartSpan span = part_span(lt, plan, p, gparams);
+    float4* dst = reinterpret_cast<float4*>(span.dst);
+    for (int i = threadIdx.x; i < span.ne / 2; i += 256) dst[i] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 constexpr int64_t kMaxBwdWorkspaceBytes = int64_t(1) << 31;  // 2 GiB (config 4: 283 MB)
@@ -988,24 +985,35 @@ int bwd_layout(int64_t N, int L, const int64_t* off, const int32_t* res, BwdLayo
 
 }  // namespace
 
+namespace {
+// The forward entry points' checks and level table (not built when N == 0:
+// the caller returns at once)
+int fwd_prologue(const char* what, int64_t N, int32_t n_levels, const float* x, const void* params,
+                 const int64_t* level_offset, const float* level_scale, const int32_t* level_res, const void* out,
+                 LevelTable* lt) {
+    if (!(N >= 0 && x && params && level_offset && level_scale && level_res && out))
+        return fail(AVR_E_ARG, std::string(what) + ": bad args");
+    return N == 0 ? 0 : make_table(n_levels, level_offset, level_scale, level_res, lt);
+}
+}  // namespace
+
 // level_offset / level_scale / level_res are HOST pointers (small metadata,
 // passed by value into the kernel argument block).
 extern "C" int avr_hashgrid_fwd(int64_t N, int32_t n_levels, const float* x, const void* params,
                                 int32_t param_dtype, const int64_t* level_offset,
                                 const float* level_scale, const int32_t* level_res, void* out,
                                 int32_t out_dtype, void* stream) {
-    AVR_REQUIRE(N >= 0 && x && params && level_offset && level_scale && level_res && out,
-                "avr_hashgrid_fwd: bad args");
-    if (N == 0) return 0;
     LevelTable lt;
-    if (int e = make_table(n_levels, level_offset, level_scale, level_res, &lt)) return e;
+    if (int e = fwd_prologue("avr_hashgrid_fwd", N, n_levels, x, params, level_offset, level_scale, level_res, out, &lt);
+        e || N == 0)
+        return e;
     const int64_t work = N * n_levels;
     const dim3 grid((unsigned)((work + 255) / 256));
     hipStream_t st = as_stream(stream);
     const int L = n_levels;
     // many points: level-major dispatch (one level's table L2-resident at a
     // time), same values and output layout (tools/probe_hashgrid.py)
-    if (N >= lm_min_points()) {
+    if (N >= kLevelMajorMinPoints) {
         const dim3 glm((unsigned)((N + 255) / 256), (unsigned)L);
         return launch_fwd_lm<true>("avr_hashgrid_fwd", glm, st, N, x, params, param_dtype, lt, out, out_dtype);
     }
@@ -1034,11 +1042,11 @@ namespace {
 int fwd_lm(int64_t N, int32_t n_levels, const float* x, const void* params, int32_t param_dtype,
            const int64_t* level_offset, const float* level_scale, const int32_t* level_res, void* out,
            int32_t out_dtype, void* stream, int unit) {
-    AVR_REQUIRE(N >= 0 && x && params && level_offset && level_scale && level_res && out,
-                "avr_hashgrid_fwd_lm: bad args");
-    if (N == 0) return 0;
     LevelTable lt;
-    if (int e = make_table(n_levels, level_offset, level_scale, level_res, &lt)) return e;
+    if (int e = fwd_prologue("avr_hashgrid_fwd_lm", N, n_levels, x, params, level_offset, level_scale, level_res, out,
+                             &lt);
+        e || N == 0)
+        return e;
     const dim3 grid((unsigned)((N + 255) / 256), (unsigned)n_levels);
     return launch_fwd_lm<false>("avr_hashgrid_fwd_lm", grid, as_stream(stream), N, x, params, param_dtype, lt, out,
                                 out_dtype, unit);
@@ -1084,36 +1092,25 @@ namespace {
 
 constexpr int kBiasRays = 4;  // 256 workgroups for config 2's 1024 rays
 
-template <typename Tp>
-__device__ __forceinline__ float2 encode_point_level(const float* xi, const Tp* params, const LevelTable& lt, int l) {
-    const Corner c = locate(xi, lt.scale[l]);
-    const uint32_t size = (uint32_t)(lt.offset[l + 1] - lt.offset[l]);
-    const uint32_t res = lt.res[l];
-    const Tp* table = params + 2 * lt.offset[l];
-    CornerAcc<Tp> acc;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        float wgt = 1.0f;
-        uint32_t g[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            if (k & (1 << d)) {
-                wgt *= c.pos[d];
-                g[d] = c.grid[d] + 1;
-            } else {
-                wgt *= 1.0f - c.pos[d];
-                g[d] = c.grid[d];
-            }
-        }
-        acc.add(wgt, CornerAcc<Tp>::load(table, grid_index(size, res, g[0], g[1], g[2])));
-    }
-    return acc.get();
-}
-
 __device__ __forceinline__ float round_feature(float v, bool f16, bool mlp_f16) {
     if (f16) v = __half2float(__float2half(v));               // the encoding's output dtype
     return mlp_f16 ? __half2float(__float2half(v))            // the MLP's 16-bit input
                    : __bfloat162float(__float2bfloat16(v));
+}
+
+// The LDS fill of both bias kernels, one feature pair: level l of ray
+// (b, r)'s direction grid or of pose b's tx grid.  The row (a ray's first
+// sample, a pose's first row) is mapped to [0, 1], encoded, and rounded as
+// the unfused path rounds it, into e[2l], e[2l + 1].
+template <typename Tp>
+__device__ __forceinline__ void bias_features(bool is_tx, int64_t b, int64_t r, int R, int S, const float* view,
+                                              const float* tx, const Tp* dp, const LevelTable& dl, const Tp* tp,
+                                              const LevelTable& tl, int l, int f16, int mlp_f16, float* e) {
+    const float* src = is_tx ? tx + b * R * S * 3 : view + (b * R * S + r * S) * 3;
+    const float xi[3] = {(src[0] + 1.0f) / 2.0f, (src[1] + 1.0f) / 2.0f, (src[2] + 1.0f) / 2.0f};
+    const float2 v = is_tx ? encode_point_level(xi, level_view(tl, l, tp)) : encode_point_level(xi, level_view(dl, l, dp));
+    e[2 * l] = round_feature(v.x, f16, mlp_f16);
+    e[2 * l + 1] = round_feature(v.y, f16, mlp_f16);
 }
 
 template <typename Tp>
@@ -1132,12 +1129,7 @@ __global__ __launch_bounds__(256) void ray_pose_bias_kernel(int B, int R, int S,
         const int which = rem / kMaxLevels, l = rem % kMaxLevels;
         if (j >= nr || l >= (which ? tL : dL)) continue;
         const int64_t gr = g0 + j;
-        const int64_t b = gr / R, r = gr % R;
-        const float* src = which ? tx + b * R * S * 3 : view + (b * R * S + r * S) * 3;
-        const float xi[3] = {(src[0] + 1.0f) / 2.0f, (src[1] + 1.0f) / 2.0f, (src[2] + 1.0f) / 2.0f};
-        const float2 v = which ? encode_point_level(xi, tp, tl, l) : encode_point_level(xi, dp, dl, l);
-        e[j][which][2 * l] = round_feature(v.x, f16, mlp_f16);
-        e[j][which][2 * l + 1] = round_feature(v.y, f16, mlp_f16);
+        bias_features(which, gr / R, gr % R, R, S, view, tx, dp, dl, tp, tl, l, f16, mlp_f16, e[j][which]);
     }
     __syncthreads();
     // sum_k e[j][which][k] * w[k][o], k ascending, 8 weight loads in flight
@@ -1175,12 +1167,10 @@ __global__ __launch_bounds__(256) void ray_pose_bias_kernel(int B, int R, int S,
 // flight at once (one L2 round trip per grid instead of one per 8 k), and the
 // pose's tx term computed once for the workgroup's rays.  The same fma chains
 // (k ascending) and the same final sd + st as ray_pose_bias_kernel: the
-// results are equal bit for bit.  4 rays per workgroup: 256 workgroups for
-// config 2's 1024 rays (15.6 us; 16.4-16.9 with 8 rays and 128 workgroups).
+// results are equal bit for bit (pinned by tests/test_gpu_model.py).  4 rays
+// per workgroup: 256 workgroups for config 2's 1024 rays (15.6 us; 16.4-16.9
+// with 8 rays and 128 workgroups).
 constexpr int kBias2Rays = 4;
-#ifndef AVR_BIAS_V1  // (A/B: 1 keeps the round-4 kernel for every R)
-#define AVR_BIAS_V1 0
-#endif
 constexpr int kBias2Threads = 512;
 
 template <typename Tp>
@@ -1196,13 +1186,7 @@ __global__ __launch_bounds__(kBias2Threads) void ray_pose_bias2_kernel(
         const int j = q / kMaxLevels, l = q % kMaxLevels;
         const bool is_tx = j == kBias2Rays;
         if (l >= (is_tx ? tL : dL)) continue;
-        const int64_t r = (g0 + j) % R;
-        const float* src = is_tx ? tx + b * R * S * 3 : view + (b * R * S + r * S) * 3;
-        const float xi[3] = {(src[0] + 1.0f) / 2.0f, (src[1] + 1.0f) / 2.0f, (src[2] + 1.0f) / 2.0f};
-        const float2 v = is_tx ? encode_point_level(xi, tp, tl, l) : encode_point_level(xi, dp, dl, l);
-        float* e = is_tx ? et : ed[j];
-        e[2 * l] = round_feature(v.x, f16, mlp_f16);
-        e[2 * l + 1] = round_feature(v.y, f16, mlp_f16);
+        bias_features(is_tx, b, (g0 + j) % R, R, S, view, tx, dp, dl, tp, tl, l, f16, mlp_f16, is_tx ? et : ed[j]);
     }
     __syncthreads();
     for (int o = threadIdx.x; o < nout; o += kBias2Threads) {
@@ -1257,7 +1241,7 @@ extern "C" int avr_ray_pose_bias(int32_t B, int32_t R, int32_t S, const float* v
     const dim3 grid((unsigned)((rays + kBiasRays - 1) / kBiasRays));
     const int f16 = enc_dtype == AVR_DTYPE_F16;
     hipStream_t st = as_stream(stream);
-    const bool v2 = R % kBias2Rays == 0 && !AVR_BIAS_V1;
+    const bool v2 = R % kBias2Rays == 0;
     return dispatch_dtype<AVR_DTYPE_F16, AVR_DTYPE_F32>(param_dtype, "avr_ray_pose_bias", [&](auto tag) {
         using Tp = typename decltype(tag)::type;
         auto go = [&](auto kern, dim3 g, dim3 block) {
@@ -1304,22 +1288,15 @@ int bwd_partitioned(int64_t N, int32_t n_levels, const float* x, const void* gra
     hipStream_t st = as_stream(stream);
     const int L = n_levels;
     const char* what = "avr_hashgrid_bwd_partitioned";
-    // the overwrite form's atomic paths (few points, shapes the partitioned
-    // passes do not take) add into a cleared gradient
-    auto clear = [&]() -> bool {
-        return !overwrite ||
-               hipMemsetAsync(grad_params, 0, (size_t)(2 * level_offset[L]) * sizeof(float), st) == hipSuccess;
-    };
-    if (N == 0) return clear() ? 0 : fail(AVR_E_ARG, "avr_hashgrid_bwd_partitioned_set: clear failed");
-    if (N < kPartitionedMinPoints) {  // few points: the atomic kernel (same += result)
-        if (!clear()) return fail(AVR_E_ARG, "avr_hashgrid_bwd_partitioned_set: clear failed");
-        return launch_bwd(what, st, N, L, x, grad_out, grad_dtype, lt, grad_params);
-    }
+    // few points (the five launches cost more), or a shape the partitioned
+    // passes do not take: the atomic kernel, the same += result.  The
+    // overwrite form adds into a cleared gradient; no points: the clear alone
     BwdLayout b;
-    if (bwd_layout(N, n_levels, level_offset, level_res, &b) != 0 || !b.scatter_ok) {
-        // shapes the partitioned passes do not take: the atomic kernel (same += result)
-        if (!clear()) return fail(AVR_E_ARG, "avr_hashgrid_bwd_partitioned_set: clear failed");
-        return launch_bwd(what, st, N, L, x, grad_out, grad_dtype, lt, grad_params);
+    if (N < kPartitionedMinPoints || bwd_layout(N, n_levels, level_offset, level_res, &b) != 0 || !b.scatter_ok) {
+        if (overwrite &&
+            hipMemsetAsync(grad_params, 0, (size_t)(2 * level_offset[L]) * sizeof(float), st) != hipSuccess)
+            return fail(AVR_E_ARG, "avr_hashgrid_bwd_partitioned_set: clear failed");
+        return N == 0 ? 0 : launch_bwd(what, st, N, L, x, grad_out, grad_dtype, lt, grad_params);
     }
     AVR_REQUIRE(workspace_bytes >= b.bytes, "avr_hashgrid_bwd_partitioned: workspace too small");
     char* ws = static_cast<char*>(workspace);

@@ -67,8 +67,7 @@ class _HashGridFn(torch.autograd.Function):
         st = torch.cuda.current_stream(x.device).cuda_stream
         table = enc.table(cache)
         _lib.call("avr_hashgrid_fwd", N, enc.n_levels, x.data_ptr(), table.data_ptr(),
-                  _code(table.dtype), enc._off.ctypes.data, enc._scale.ctypes.data,
-                  enc._res.ctypes.data, out.data_ptr(), _code(out.dtype), st)
+                  _code(table.dtype), *enc.level_meta(), out.data_ptr(), _code(out.dtype), st)
         ctx.enc = enc
         ctx.save_for_backward(x)
         return out
@@ -86,8 +85,7 @@ class _HashGridFn(torch.autograd.Function):
         if mode == "atomic":
             gp = torch.zeros(enc.n_params, dtype=torch.float32, device=x.device)
             _lib.call("avr_hashgrid_bwd", N, enc.n_levels, x.data_ptr(), g.data_ptr(),
-                      _code(g.dtype), enc._off.ctypes.data, enc._scale.ctypes.data,
-                      enc._res.ctypes.data, gp.data_ptr(), st)
+                      _code(g.dtype), *enc.level_meta(), gp.data_ptr(), st)
             return None, gp, None, None
         # partitioned (no global atomics), written rather than added: no
         # clearing pass over the table ("partitioned_add": the += form into
@@ -99,8 +97,7 @@ class _HashGridFn(torch.autograd.Function):
         ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=x.device)
         _lib.call("avr_hashgrid_bwd_partitioned" if add else "avr_hashgrid_bwd_partitioned_set", N, enc.n_levels,
                   x.data_ptr(), g.data_ptr(),
-                  _code(g.dtype), enc._off.ctypes.data, enc._scale.ctypes.data, enc._res.ctypes.data,
-                  gp.data_ptr(), ws.data_ptr(), nbytes.value, st)
+                  _code(g.dtype), *enc.level_meta(), gp.data_ptr(), ws.data_ptr(), nbytes.value, st)
         return None, gp, None, None
 
 
@@ -135,6 +132,11 @@ class HashGridEncoding(nn.Module):
         init = (torch.rand(self.n_params, generator=g) * 2 - 1) * 1e-4
         self.params = nn.Parameter(init)
 
+    def level_meta(self):
+        """Host pointers of the level metadata (offsets, scales, resolutions),
+        in the order every hash-grid entry point takes them."""
+        return self._off.ctypes.data, self._scale.ctypes.data, self._res.ctypes.data
+
     def table(self, cache=False):
         """The level tables in the module's param precision."""
         return cast_weight(self.params, self.param_dtype, cache)
@@ -153,8 +155,7 @@ class HashGridEncoding(nn.Module):
         table = self.table(not torch.is_grad_enabled())
         fn = "avr_hashgrid_fwd_lm_unit" if unit_map else "avr_hashgrid_fwd_lm"
         _lib.call(fn, N, self.n_levels, x.data_ptr(), table.data_ptr(),
-                  _code(table.dtype), self._off.ctypes.data, self._scale.ctypes.data,
-                  self._res.ctypes.data, out.data_ptr(), _code(out.dtype), st)
+                  _code(table.dtype), *self.level_meta(), out.data_ptr(), _code(out.dtype), st)
         return out
 
     def forward(self, x):

@@ -672,9 +672,8 @@ def _ray_pose_bias(dir_enc, tx_enc, view, tx, wd, wt, layout, mlp_dtype=torch.bf
     bias = torch.empty(B * R, wd.size(1), dtype=torch.float32, device=view.device)
     st = torch.cuda.current_stream(view.device).cuda_stream
     _lib.call("avr_ray_pose_bias", B, R, S, v.data_ptr(), t.data_ptr(),
-              dir_enc.n_levels, dtab.data_ptr(), dir_enc._off.ctypes.data, dir_enc._scale.ctypes.data,
-              dir_enc._res.ctypes.data, tx_enc.n_levels, ttab.data_ptr(), tx_enc._off.ctypes.data,
-              tx_enc._scale.ctypes.data, tx_enc._res.ctypes.data, _code(dtab.dtype), _code(dir_enc.dtype),
+              dir_enc.n_levels, dtab.data_ptr(), *dir_enc.level_meta(),
+              tx_enc.n_levels, ttab.data_ptr(), *tx_enc.level_meta(), _code(dtab.dtype), _code(dir_enc.dtype),
               _lib.DTYPE_F16 if mlp_dtype == torch.float16 else _lib.DTYPE_BF16,
               wd.data_ptr(), wt.data_ptr(), wd.size(1), bias.data_ptr(), st)
     return bias

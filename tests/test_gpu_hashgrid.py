@@ -173,7 +173,7 @@ def test_partitioned_backward_accumulates(n):
     L = enc.n_levels
     g = torch.randn(n, 2 * L, device=DEV).half()
     st = torch.cuda.current_stream(DEV).cuda_stream
-    meta = (enc._off.ctypes.data, enc._scale.ctypes.data, enc._res.ctypes.data)
+    meta = enc.level_meta()
     a = torch.zeros(enc.n_params, device=DEV)
     _lib.call("avr_hashgrid_bwd", n, L, x.data_ptr(), g.data_ptr(), _code(g.dtype), *meta, a.data_ptr(), st)
     nb = ctypes.c_int64()
@@ -207,7 +207,7 @@ def test_partitioned_backward_set_overwrites(n):
     L = enc.n_levels
     g = torch.randn(n, 2 * L, device=DEV).half()
     st = torch.cuda.current_stream(DEV).cuda_stream
-    meta = (enc._off.ctypes.data, enc._scale.ctypes.data, enc._res.ctypes.data)
+    meta = enc.level_meta()
     nb = ctypes.c_int64()
     _lib.call("avr_hashgrid_bwd_workspace", n, L, enc._off.ctypes.data, ctypes.byref(nb))
     ws = torch.empty(max(nb.value, 256), dtype=torch.uint8, device=DEV)
@@ -250,7 +250,7 @@ def test_partitioned_backward_scatter_above_64k_lds(log2):
     x_host = _points(n, 16)
     x = torch.from_numpy(x_host).to(DEV)
     st = torch.cuda.current_stream(DEV).cuda_stream
-    meta = (enc._off.ctypes.data, enc._scale.ctypes.data, enc._res.ctypes.data)
+    meta = enc.level_meta()
     nb = ctypes.c_int64()
     _lib.call("avr_hashgrid_bwd_workspace", n, L, enc._off.ctypes.data, ctypes.byref(nb))
     assert nb.value > 256  # the partitioned passes, not the atomic fallback

@@ -154,9 +154,10 @@ def test_ray_pose_bias_kernel_matches_torch_ops(enc_dtype, workload):
     """avr_ray_pose_bias against the torch ops it replaces in the fused
     inference trunk: per-ray / per-pose selection, (x + 1) / 2, the dir and tx
     grids, fp16 -> bf16 -> fp32 rounding, two skinny fp32 GEMMs and their sum
-    (only the GEMMs' fp32 summation order differs).  Config 2 (1024 rays per
-    pose) takes the one-pose-per-workgroup kernel, config 5 (4094 rays, not a
-    multiple of 8) the general one."""
+    (only the GEMMs' fp32 summation order differs).  Both workloads' ray
+    counts (1024 and 4096 per pose) are multiples of 4, so both take the
+    one-pose-per-workgroup kernel; the general one is run by
+    test_ray_pose_bias_general_kernel_equals_one_pose_kernel."""
     from avr_amd.model import _bias_columns, _per_pose, _per_ray, _ray_pose_bias
 
     w = WORKLOADS[workload]
@@ -183,6 +184,42 @@ def test_ray_pose_bias_kernel_matches_torch_ops(enc_dtype, workload):
     with torch.no_grad():
         again = _ray_pose_bias(model._dir_encoding, model._tx_encoding, view, tx, wd, wt, L)
     assert torch.equal(got, again)
+
+
+@pytest.mark.parametrize("enc_dtype", [torch.float16, torch.float32])
+def test_ray_pose_bias_general_kernel_equals_one_pose_kernel(enc_dtype):
+    """The same 12 rays as one pose of 12 (R % 4 == 0: the one-pose-per-
+    workgroup kernel) and as two poses of 6 with the same tx (R % 4 == 2: the
+    general kernel, whose middle workgroup spans both poses): equal bit for
+    bit, as hashgrid.hip states, and close to the torch ops.  Ten features
+    per grid: the 8-wide block and the tail of the general kernel's k loop,
+    a partial 16-wide block of the other's."""
+    from avr_amd.encoding import HashGridEncoding
+    from avr_amd.model import _per_pose, _per_ray, _ray_pose_bias
+
+    g = torch.Generator(device=DEV).manual_seed(7)
+    cfg = dict(n_levels=5, log2_hashmap_size=12, base_resolution=4)
+    dir_enc = HashGridEncoding(3, cfg, dtype=enc_dtype).to(DEV)
+    tx_enc = HashGridEncoding(3, cfg, dtype=enc_dtype).to(DEV)
+    with torch.no_grad():
+        for enc in (dir_enc, tx_enc):
+            enc.params.uniform_(-1, 1, generator=g)
+    wd = torch.randn(10, 33, device=DEV, generator=g)
+    wt = torch.randn(10, 33, device=DEV, generator=g)
+    S = 2
+    view = torch.rand(1, 12 * S, 3, device=DEV, generator=g) * 2 - 1
+    tx = (torch.rand(1, 1, 3, device=DEV, generator=g) * 2 - 1).expand(1, 12 * S, 3).contiguous()
+    one_pose, two_poses = (1, 12, S), (2, 6, S)
+    with torch.no_grad():
+        a = _ray_pose_bias(dir_enc, tx_enc, view, tx, wd, wt, one_pose)
+        b = _ray_pose_bias(dir_enc, tx_enc, view, tx, wd, wt, two_poses)
+        dir_e = dir_enc((_per_ray(view.reshape(-1, 3), one_pose) + 1) / 2)
+        tx_e = tx_enc((_per_pose(tx.reshape(-1, 3), one_pose) + 1) / 2)
+        ref = dir_e.to(torch.bfloat16).float() @ wd + tx_e.to(torch.bfloat16).float() @ wt
+    assert a is not None and b is not None and a.shape == b.shape == ref.shape == (12, 33)
+    for got in (a, b):
+        torch.testing.assert_close(got, ref, rtol=1e-5, atol=1e-6 * float(ref.abs().max()))
+    assert torch.equal(a, b), float((a - b).abs().max())
 
 
 def test_unit_map_is_bit_identical():

@@ -63,8 +63,7 @@ def main():
 
     def bwd_part():
         _lib.call("avr_hashgrid_bwd_partitioned", N, L, x.data_ptr(), gout.data_ptr(), _code(gout.dtype),
-                  enc._off.ctypes.data, enc._scale.ctypes.data, enc._res.ctypes.data, gp.data_ptr(),
-                  ws.data_ptr(), nb.value, st)
+                  *enc.level_meta(), gp.data_ptr(), ws.data_ptr(), nb.value, st)
 
     def time_us(fn):
         for _ in range(3):

@@ -63,9 +63,7 @@ def main():
 
     def call(lib, ws, gp):
         rc = lib.avr_hashgrid_bwd_partitioned_set(N, L, x.data_ptr(), gout.data_ptr(), _code(gout.dtype),
-                                                  enc._off.ctypes.data, enc._scale.ctypes.data,
-                                                  enc._res.ctypes.data, gp.data_ptr(), ws.data_ptr(),
-                                                  ws.numel(), st)
+                                                  *enc.level_meta(), gp.data_ptr(), ws.data_ptr(), ws.numel(), st)
         if rc:
             raise RuntimeError(lib.avr_last_error().decode())
 
