@@ -44,7 +44,13 @@ class Case:
 
 
 def digest_check(case, name, actual, rtol=0.0, atol=0.0):
-    """Compare `actual` (numpy) to a stored digest (full array or samples)."""
+    """Compare `actual` (numpy) to a stored digest (full array or samples)
+    and, where the fixture holds it, to the stored sum of the whole array.
+
+    The sum's bound is what element-wise closeness at (rtol, atol) implies:
+    |sum(actual) - sum(ref)| <= n*atol + rtol*sum|ref|, and sum|ref| <=
+    sqrt(n * sumsq) by Cauchy-Schwarz.  It reaches the elements a sampled
+    digest leaves out."""
     a = np.asarray(actual)
     if case.has(name):
         np.testing.assert_allclose(a, case[name], rtol=rtol, atol=atol)
@@ -53,6 +59,10 @@ def digest_check(case, name, actual, rtol=0.0, atol=0.0):
         np.testing.assert_allclose(flat[case[name + "_idx"]], case[name + "_at"], rtol=rtol, atol=atol)
     s = float(a.astype(np.float64).sum())
     ss = float((a.astype(np.float64) ** 2).sum())
+    if case.has(name + "_sum"):
+        ref_s, ref_ss = float(case[name + "_sum"]), float(case[name + "_sumsq"])
+        bound = a.size * atol + rtol * np.sqrt(a.size * ref_ss)
+        assert abs(s - ref_s) <= bound, f"{name}: sum {s!r} vs stored {ref_s!r}, |diff| {abs(s - ref_s):.3e} > {bound:.3e}"
     return s, ss
 
 
