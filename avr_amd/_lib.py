@@ -141,6 +141,9 @@ _SIGS = {
                                                     _c_i64, _vp]),
     "avr_hashgrid_bwd_partitioned_set": (ctypes.c_int, [_c_i64, _c_i32, _vp, _vp, _c_i32, _vp, _vp, _vp, _vp, _vp,
                                                     _c_i64, _vp]),
+    "avr_hashgrid_bwd_input_workspace": (ctypes.c_int, [_c_i64, _c_i32, _vp]),
+    "avr_hashgrid_bwd_input": (ctypes.c_int, [_c_i64, _c_i32, _vp, _vp, _c_i32, _vp, _c_i32, _vp, _vp, _vp, _vp, _vp,
+                                              _c_i64, _vp]),
     "avr_linear_wgrad_splits": (ctypes.c_int, [_c_i64, _c_i32, _c_i32, _vp]),
     "avr_linear512_pack_w2": (ctypes.c_int, [_vp, _c_i32, _c_i32, _vp, _vp]),
     "avr_linear512_mask_fwd": (ctypes.c_int, [_c_i64, _vp, _vp, _c_i32, _vp, _vp, _vp]),

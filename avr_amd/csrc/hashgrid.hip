@@ -166,6 +166,29 @@ __device__ __forceinline__ void corner(const Corner& c, int k, uint32_t size, ui
     e = grid_index(size, res, g[0], g[1], g[2]);
 }
 
+// Corner k's part in the derivative of the trilinear interpolant with respect
+// to the point, in cell units (the caller multiplies by the level's scale):
+// dw[d] = s_d(k) * prod_{e != d} omega_e(k), with corner()'s omega (frac where
+// bit e of k is set, 1 - frac otherwise) and s_d(k) = +1 where bit d is set,
+// -1 otherwise; e is corner()'s entry.  The one place that holds the sign
+// and weight rule of the input gradient.
+__device__ __forceinline__ void corner_dx(const Corner& c, int k, uint32_t size, uint32_t res, float (&dw)[3],
+                                          uint32_t& e) {
+    float om[3];
+    uint32_t g[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const bool up = k & (1 << d);
+        om[d] = up ? c.pos[d] : 1.0f - c.pos[d];
+        g[d] = up ? c.grid[d] + 1 : c.grid[d];
+    }
+    const float w12 = om[1] * om[2], w02 = om[0] * om[2], w01 = om[0] * om[1];
+    dw[0] = (k & 1) ? w12 : -w12;
+    dw[1] = (k & 2) ? w02 : -w02;
+    dw[2] = (k & 4) ? w01 : -w01;
+    e = grid_index(size, res, g[0], g[1], g[2]);
+}
+
 // The feature pair of point xi at one level: the corner sum in index order
 template <typename Tp>
 __device__ __forceinline__ float2 encode_point_level(const float* xi, const Level<const Tp>& lv) {
@@ -296,6 +319,58 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_lm_kernel(int64_t N, const f
         for (int k = 0; k < 8; ++k) acc.add(wgt[k], CornerAcc<Tp>::load(table, ent[k]));
     }
     store_pair(out, ROW_MAJOR ? i * (int64_t)gridDim.y + l : (int64_t)l * N + i, acc.get());
+}
+
+// Input gradient: dL/dx of the trilinear interpolant at the forward's own
+// cell (locate, corner_dx), all in fp32 with table and gradient values upcast
+// exactly.  Two passes, for every N:
+//   1. level-major, grid (points / 256, L) as hashgrid_fwd_lm_kernel: the
+//      blocks in flight gather from one or two levels' tables, which stay in
+//      each XCD's L2.  A thread owns (point i, level l), gathers the forward's
+//      8 entries and writes scale_l * sum_k dw_k[d] * (g0 v0 + g1 v1)
+//      (k ascending) to partial[l][i][d];
+//   2. one thread per (i, d) sums partial[.][i][d] over l ascending.
+// No atomics and a fixed order everywhere: bitwise repeatable, and the same
+// bits whatever N is.
+template <typename Tp, typename Tg>
+__global__ __launch_bounds__(256) void hashgrid_dx_level_kernel(int64_t N, const float* __restrict__ x,
+                                                                const Tp* __restrict__ params,
+                                                                const Tg* __restrict__ gout, LevelTable lt,
+                                                                float* __restrict__ partial) {
+    const int l = blockIdx.y, L = gridDim.y;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const float xi[3] = {x[i * 3 + 0], x[i * 3 + 1], x[i * 3 + 2]};
+    const float g0 = load_f(gout, i * (2 * L) + 2 * l), g1 = load_f(gout, i * (2 * L) + 2 * l + 1);
+    const Level<const Tp> lv = level_view(lt, l, params);
+    const Corner c = locate(xi, lv.scale);
+    float dw[8][3];
+    uint32_t ent[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) corner_dx(c, k, lv.size, lv.res, dw[k], ent[k]);
+    float2 v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = load_pair<Tp>(lv.table, ent[k]);
+    float acc[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float t = fmaf(g1, v[k].y, g0 * v[k].x);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) acc[d] = fmaf(dw[k][d], t, acc[d]);
+    }
+    float* p = partial + ((int64_t)l * N + i) * 3;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) p[d] = lv.scale * acc[d];
+}
+
+// grad_x[j] = sum_l partial[l][j], l ascending, for the M = 3 N components j
+__global__ __launch_bounds__(256) void hashgrid_dx_sum_kernel(int64_t M, int L, const float* __restrict__ partial,
+                                                              float* __restrict__ grad_x) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= M) return;
+    float s = 0.0f;
+    for (int l = 0; l < L; ++l) s += partial[(int64_t)l * M + j];
+    grad_x[j] = s;
 }
 
 // Backward: scatter-add of w_corner * dL/dy into the tables.
@@ -1362,4 +1437,46 @@ extern "C" int avr_hashgrid_bwd_partitioned_set(int64_t N, int32_t n_levels, con
                                                 void* stream) {
     return bwd_partitioned(N, n_levels, x, grad_out, grad_dtype, level_offset, level_scale, level_res, grad_params,
                            workspace, workspace_bytes, stream, true);
+}
+
+// ------------------------------------------------ input gradient (dL/dx)
+// Workspace of avr_hashgrid_bwd_input: the per-level partials [L][N][3] fp32.
+extern "C" int avr_hashgrid_bwd_input_workspace(int64_t N, int32_t n_levels, int64_t* bytes) {
+    AVR_REQUIRE(N >= 0 && bytes, "avr_hashgrid_bwd_input_workspace: bad args");
+    AVR_REQUIRE(n_levels >= 1 && n_levels <= kMaxLevels, "hashgrid: n_levels out of range (1..32)");
+    *bytes = std::max<int64_t>(256, N * n_levels * 3 * (int64_t)sizeof(float));
+    return 0;
+}
+
+extern "C" int avr_hashgrid_bwd_input(int64_t N, int32_t n_levels, const float* x, const void* params,
+                                      int32_t param_dtype, const void* grad_out, int32_t grad_dtype,
+                                      const int64_t* level_offset, const float* level_scale,
+                                      const int32_t* level_res, float* grad_x, void* workspace,
+                                      int64_t workspace_bytes, void* stream) {
+    const char* what = "avr_hashgrid_bwd_input";
+    AVR_REQUIRE(N >= 0 && x && params && grad_out && level_offset && level_scale && level_res && grad_x && workspace,
+                "avr_hashgrid_bwd_input: bad args");
+    AVR_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0,
+                "avr_hashgrid_bwd_input: workspace must be 16-byte aligned");
+    if (N == 0) return 0;
+    LevelTable lt;
+    if (int e = make_table(n_levels, level_offset, level_scale, level_res, &lt)) return e;
+    const int L = n_levels;
+    AVR_REQUIRE(N <= (int64_t(1) << 36), "avr_hashgrid_bwd_input: too many points");  // both grids' x extents
+    AVR_REQUIRE(workspace_bytes >= N * L * 3 * (int64_t)sizeof(float), "avr_hashgrid_bwd_input: workspace too small");
+    hipStream_t st = as_stream(stream);
+    float* partial = static_cast<float*>(workspace);
+    const dim3 grid((unsigned)((N + 255) / 256), (unsigned)L);
+    if (int e = dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16>(param_dtype, what, [&](auto pt) {
+            return dispatch_dtype<AVR_DTYPE_F32, AVR_DTYPE_F16>(grad_dtype, what, [&](auto gt) {
+                using Tp = typename decltype(pt)::type;
+                using Tg = typename decltype(gt)::type;
+                return launch(what, hashgrid_dx_level_kernel<Tp, Tg>, grid, dim3(256), 0, st, N, x, (const Tp*)params,
+                              (const Tg*)grad_out, lt, partial);
+            });
+        }))
+        return e;
+    const int64_t M = 3 * N;
+    return launch(what, hashgrid_dx_sum_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, M, L,
+                  (const float*)partial, grad_x);
 }

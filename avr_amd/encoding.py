@@ -69,8 +69,23 @@ class _HashGridFn(torch.autograd.Function):
         _lib.call("avr_hashgrid_fwd", N, enc.n_levels, x.data_ptr(), table.data_ptr(),
                   _code(table.dtype), *enc.level_meta(), out.data_ptr(), _code(out.dtype), st)
         ctx.enc = enc
+        # the points' gradient (pose refinement) reads the tables the forward
+        # read: kept only when x requires grad
+        ctx.table = table if ctx.needs_input_grad[0] else None
         ctx.save_for_backward(x)
         return out
+
+    @staticmethod
+    def _grad_x(ctx, x, g, st):
+        """dL/dx [N, 3] fp32 (avr_hashgrid_bwd_input)."""
+        enc, table, N = ctx.enc, ctx.table, x.size(0)
+        gx = torch.empty(N, 3, dtype=torch.float32, device=x.device)
+        nbytes = ctypes.c_int64()
+        _lib.call("avr_hashgrid_bwd_input_workspace", N, enc.n_levels, ctypes.byref(nbytes))
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=x.device)
+        _lib.call("avr_hashgrid_bwd_input", N, enc.n_levels, x.data_ptr(), table.data_ptr(), _code(table.dtype),
+                  g.data_ptr(), _code(g.dtype), *enc.level_meta(), gx.data_ptr(), ws.data_ptr(), nbytes.value, st)
+        return gx
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -81,12 +96,17 @@ class _HashGridFn(torch.autograd.Function):
             g = g.float()
         st = torch.cuda.current_stream(x.device).cuda_stream
         N = x.size(0)
+        gx = None
+        if ctx.needs_input_grad[0]:
+            gx = _HashGridFn._grad_x(ctx, x, g, st)
+            if not ctx.needs_input_grad[1]:  # a frozen grid: no table gradient to form
+                return gx, None, None, None
         mode = enc.options.hashgrid_bwd
         if mode == "atomic":
             gp = torch.zeros(enc.n_params, dtype=torch.float32, device=x.device)
             _lib.call("avr_hashgrid_bwd", N, enc.n_levels, x.data_ptr(), g.data_ptr(),
                       _code(g.dtype), *enc.level_meta(), gp.data_ptr(), st)
-            return None, gp, None, None
+            return gx, gp, None, None
         # partitioned (no global atomics), written rather than added: no
         # clearing pass over the table ("partitioned_add": the += form into
         # a cleared table, for A/B); workspace from the caching allocator
@@ -98,7 +118,7 @@ class _HashGridFn(torch.autograd.Function):
         _lib.call("avr_hashgrid_bwd_partitioned" if add else "avr_hashgrid_bwd_partitioned_set", N, enc.n_levels,
                   x.data_ptr(), g.data_ptr(),
                   _code(g.dtype), *enc.level_meta(), gp.data_ptr(), ws.data_ptr(), nbytes.value, st)
-        return None, gp, None, None
+        return gx, gp, None, None
 
 
 class HashGridEncoding(nn.Module):

@@ -134,6 +134,10 @@ class GraphedRender:
         if ray_gain is not None:
             raise NotImplementedError("GraphedRender does not take ray_gain (directional receivers "
                                       "render through AVRRender)")
+        if torch.is_grad_enabled() and (rays_o.requires_grad or position_tx.requires_grad or
+                                        (direction_tx is not None and direction_tx.requires_grad)):
+            raise NotImplementedError("GraphedRender replays a forward-only graph: render poses that require "
+                                      "grad through AVRRender")
         r = self.renderer
         # the device without r._device's availability check and torch.device
         # construction on every call (~1 us of the serial pose); a host pose

@@ -565,6 +565,52 @@ def ray_directions(n_azi, n_ele, random_azi=True, device=None):
 
 
 # --------------------------------------------------------------------------
+# pose gradients: the sampling stage as an autograd node
+# --------------------------------------------------------------------------
+class _SamplePoses(torch.autograd.Function):
+    """`AVRRender.sample` for poses that require grad.  The forward makes the
+    constant-pose kernel calls (the same values bit for bit); the network
+    inputs are affine in the poses, per axis with k = 2 / (xyz_max - xyz_min):
+
+        pts = normalize(rays_o + dir d)   -> grad_rays_o[b]      = k sum_n grad_pts[b, n]
+        tx  = normalize(position_tx)      -> grad_position_tx[b] = k sum_n grad_tx[b, n]
+        dir_tx = direction_tx             -> grad_direction_tx[b] = sum_n grad_dir_tx[b, n]
+
+    (sums in fp32).  `view` depends on no pose, and the delays and masks of
+    the render core come from round(): no gradient, here as in the reference,
+    so geom carries the poses detached."""
+
+    @staticmethod
+    def forward(ctx, render, u_azi, rays_o, position_tx, direction_tx):
+        poses = (rays_o, position_tx, direction_tx)
+        pts, view, tx, dtx, geom = render._sample(
+            *(None if t is None else t.detach() for t in poses), u_azi)
+        ctx.k = 2.0 / render._params(2, geom["n_rays"]).span
+        ctx.like = [None if t is None else (t.shape, t.dtype, t.device) for t in poses]
+        # (an input of a constant pose stays constant: the network forms no
+        # gradient for it)
+        need = ctx.needs_input_grad[2:]
+        ctx.mark_non_differentiable(view, *(t for t, n in zip((pts, tx, dtx), need) if t is not None and not n))
+        ctx.set_materialize_grads(False)
+        return pts, tx, dtx, view, geom
+
+    @staticmethod
+    def backward(ctx, g_pts, g_tx, g_dtx, *_):
+        def pose_grad(g, like, k, need):
+            if g is None or like is None or not need:
+                return None
+            s = g.sum(dim=1, dtype=torch.float32)
+            if k is not None:
+                s = s * k
+            shape, dtype, device = like
+            return s.to(device=device, dtype=dtype).reshape(shape)
+
+        need = ctx.needs_input_grad
+        return (None, None, pose_grad(g_pts, ctx.like[0], ctx.k, need[2]),
+                pose_grad(g_tx, ctx.like[1], ctx.k, need[3]), pose_grad(g_dtx, ctx.like[2], None, need[4]))
+
+
+# --------------------------------------------------------------------------
 # the drop-in module
 # --------------------------------------------------------------------------
 class AVRRender(nn.Module):
@@ -627,7 +673,26 @@ class AVRRender(nn.Module):
         (ray sharding, avr_amd.parallel) only rays [r0, r1) are sampled; the
         jitter draw and the full direction set are still computed so every
         shard sees the same sphere.
+
+        With autograd recording and a pose (`rays_o`, `position_tx` or
+        `direction_tx`) that requires grad, the same kernel calls run inside
+        `_SamplePoses`: pts, tx and dir_tx then carry the pose gradient (the
+        delays are rounded and carry none, so geom holds detached poses).
         """
+        if torch.is_grad_enabled() and any(
+                t is not None and t.requires_grad for t in (rays_o, position_tx, direction_tx)):
+            if self._staged is not None or self._jitter_dev is not None:
+                raise NotImplementedError("pose gradients through a staged or graph-captured pose: render "
+                                          "eagerly with AVRRender for poses that require grad")
+            if self.ray_range is not None:
+                raise NotImplementedError("pose gradients with sharded rays (ray_range): the shards' pose "
+                                          "gradients are not summed")
+            pts, tx, dtx, view, geom = _SamplePoses.apply(self, u_azi, rays_o, position_tx, direction_tx)
+            return pts, view, tx, dtx, geom
+        return self._sample(rays_o, position_tx, direction_tx, u_azi)
+
+    def _sample(self, rays_o, position_tx, direction_tx=None, u_azi=None):
+        """sample() on constant poses: the kernel calls, no autograd node."""
         if self._staged is not None:
             return self._sample_staged(position_tx.size(0), direction_tx is not None)
         dev = self._device(rays_o)

@@ -342,6 +342,21 @@ int avr_hashgrid_bwd_partitioned_set(int64_t N, int32_t n_levels, const float* x
                                      const int32_t* level_res, float* grad_params, void* workspace,
                                      int64_t workspace_bytes, void* stream);
 
+/* The encoding's gradient with respect to the points: grad_x[N][3] (fp32) =
+ * sum over levels (ascending) and features of grad_out[N][L*2] times the
+ * derivative of the trilinear interpolant at the forward's own cell (the
+ * same fp32 p = fma(scale, x, 0.5), floor, frac and table entries), fp32
+ * arithmetic on exactly upcast table and gradient values.  No atomics, fixed
+ * summation order: bitwise repeatable.  Piecewise: the derivative is that of
+ * the cell the forward chose, also on a cell face.  workspace: 16-byte
+ * aligned, avr_hashgrid_bwd_input_workspace bytes (N * n_levels * 12). */
+int avr_hashgrid_bwd_input_workspace(int64_t N, int32_t n_levels, int64_t* bytes);
+int avr_hashgrid_bwd_input(int64_t N, int32_t n_levels, const float* x, const void* params,
+                           int32_t param_dtype, const void* grad_out, int32_t grad_dtype,
+                           const int64_t* level_offset, const float* level_scale,
+                           const int32_t* level_res, float* grad_x, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+
 /* ---- a6: weight gradient of the networks' bias-free linear layers -------
  * grad_w[M][K] (fp32) = sum_n grad_y[n][M] * x[n][K], both operands bf16,
  * row-major, 16-byte aligned, M and K multiples of 8.  Replaces the wgrad
