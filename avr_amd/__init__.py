@@ -11,6 +11,7 @@ from .renderer import (  # noqa: F401
     denormalize_points,
     normalize_points,
     ray_directions,
+    sh_decode,
     spectrum_to_ir,
 )
 from .criterion import Criterion  # noqa: F401

@@ -120,6 +120,11 @@ _SIGS = {
     "avr_ray_reduce_mc_fwd": (ctypes.c_int, [_vp, _c_i32, _c_i32, _vp, _c_i32, _vp, _vp, _vp, _c_i64, _c_i32,
                                              _vp, _vp]),
     "avr_reduce_mc_splits": (ctypes.c_int, [_vp, _c_i32, _c_i32, _c_i32, _vp, _vp]),
+    "avr_ray_reduce_mc16_fwd": (ctypes.c_int, [_vp, _c_i32, _c_i32, _vp, _c_i32, _vp, _vp, _vp, _c_i64, _c_i32,
+                                               _vp, _vp]),
+    "avr_reduce_mc16_max_rays": (_c_i32, []),
+    "avr_sh_decode_fwd": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, _c_i32, _vp, _vp, _vp, _vp]),
+    "avr_sh_decode_bwd": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, _c_i32, _vp, _vp, _vp, _vp]),
     "avr_ray_reduce_mc_bwd": (ctypes.c_int, [_vp, _c_i32, _c_i32, _vp, _c_i32, _vp, _vp, _vp, _vp, _c_i64,
                                              _vp, _vp, _vp]),
     "avr_dft_phase_fwd": (ctypes.c_int, [_vp, _c_i32, _vp, _c_i32, _vp, _vp, _vp, _vp, _c_i32, _vp, _vp]),

@@ -195,7 +195,7 @@ def synth_trajectory(spec, x, hop, fade=None):
 
 
 def auralize_path(renderer, rays_o, position_tx, x, hop, fade=None, direction_tx=None, ch_idx=None,
-                  ray_gain=None, pose_chunk=64):
+                  ray_gain=None, pose_chunk=64, sh_decoder=None):
     """`x` heard while moving through the rendered field: the P poses
     `rays_o` [P, 3] (listener) and `position_tx` [P, 3] or [3] (source;
     `direction_tx` [P, 3] or [3] and `ch_idx` [P] or one value where the
@@ -204,7 +204,11 @@ def auralize_path(renderer, rays_o, position_tx, x, hop, fade=None, direction_tx
     and `x` is convolved along them (`convolve_trajectory`).  Returns
     [C, L+T-1]: C = 1 for the omnidirectional receiver, the channels of
     `ray_gain` ([C, R] or a callable, see `AVRRender.forward`; a per-pose
-    gain [P, C, R] is cut with the poses) for a directional one.
+    gain [P, C, R], or a callable with `per_pose` set such as
+    `spatial.ambisonic(3, rotation=heads)` with P head rotations, is cut with
+    the poses) for a directional one, the E ears of `sh_decoder` (see
+    `AVRRender.forward`) where one is given: with both, a head-tracked
+    binaural walk through the field.
 
     The azimuth jitter is drawn once (`draw_jitter`, the CPU generator's two
     draws of one render) and handed to every chunk: all points of the path
@@ -235,16 +239,18 @@ def auralize_path(renderer, rays_o, position_tx, x, hop, fade=None, direction_tx
         if ch_idx.numel() not in (1, P):
             raise ValueError(f"auralize_path: ch_idx needs 1 or {P} entries, got {ch_idx.numel()}")
         ch_idx = ch_idx.expand(P)
-    per_pose_gain = isinstance(ray_gain, torch.Tensor) and ray_gain.dim() == 3
-    if per_pose_gain and ray_gain.size(0) != P:
-        raise ValueError(f"auralize_path: a per-pose ray_gain needs {P} poses, got {ray_gain.size(0)}")
+    per_pose_gain = (isinstance(ray_gain, torch.Tensor) and ray_gain.dim() == 3) or \
+        bool(getattr(ray_gain, "per_pose", False))
+    if per_pose_gain and len(ray_gain) != P:
+        raise ValueError(f"auralize_path: a per-pose ray_gain needs {P} poses, got {len(ray_gain)}")
     u_azi = draw_jitter(renderer.n_azi, renderer.n_ele)
     irs = []
     with torch.no_grad():
         for i in range(0, P, pose_chunk):
             s = slice(i, i + pose_chunk)
             _, ir = renderer.render_ir(rays_o[s], position_tx[s], None if direction_tx is None else direction_tx[s],
-                                       None if ch_idx is None else ch_idx[s], ray_gain=ray_gain[s] if per_pose_gain else ray_gain, u_azi=u_azi)
+                                       None if ch_idx is None else ch_idx[s], ray_gain=ray_gain[s] if per_pose_gain else ray_gain,
+                                       u_azi=u_azi, **({} if sh_decoder is None else {"sh_decoder": sh_decoder}))
             irs.append(ir.reshape(ir.size(0), -1, ir.size(-1)))
     return convolve_trajectory(irs[0] if len(irs) == 1 else torch.cat(irs), x, hop, fade)
 

@@ -31,6 +31,10 @@ int device_cus();
         if (!(cond)) return ::avr::fail(AVR_E_ARG, msg); \
     } while (0)
 
+// The range checks every render entry point makes on its params
+// (render_fwd.hip); 0, or the status already recorded with fail().
+int validate_render_params(const avr_render_params* p);
+
 // irfft of B spectra [B][F][2] -> [B][2(F-1)], and of a second batch
 // (spec2 -> ir2, may be null) in the same launch (render_fwd.hip).
 int launch_irfft(int B, int F, const float* spec, const float* spec2, const float* tw, float* ir,

@@ -23,6 +23,19 @@ constexpr int kReduceRows = 4;
 constexpr int kMaxChannels = 16;
 constexpr int mc_block(int left) { return left >= 4 ? 4 : left >= 2 ? 2 : 1; }
 
+// The one-pass form of up to 16 channels (render_mc16.hip): a wave takes a
+// strip of 16 chunks and walks the rays in batches of kMc16Batch groups of 4
+// (the k of v_mfma_f32_16x16x4_f32); at most kMc16Waves waves per workgroup
+// loop over the strips of a row.  Its LDS slab holds a delay and 16 products
+// w*g per ray, the rays padded to whole batches, and may use a CU's 160 KiB.
+constexpr int kMc16Waves = 8;
+template <int VEC>
+constexpr int kMc16Batch = VEC == 4 ? 8 : 4;
+constexpr int kMc16RayBytes = 4 + 4 * kMaxChannels;
+constexpr int kMc16RayPad = 32;  // 4 * the largest kMc16Batch
+constexpr int mc16_max_rays() { return (int)(160 * 1024 / kMc16RayBytes) / kMc16RayPad * kMc16RayPad; }
+constexpr int mc16_padded(int rays) { return ((rays < 1 ? 1 : rays) + kMc16RayPad - 1) & ~(kMc16RayPad - 1); }
+
 // The 16-byte vector form needs every signal-shaped tensor 16-byte aligned
 // and rows of one (b, s) column at one alignment phase: S*T % VEC == 0.
 template <typename Tin, typename... Ptr>

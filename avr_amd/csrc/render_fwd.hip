@@ -1235,6 +1235,8 @@ extern "C" int avr_spectrum_finalize(int32_t B, int32_t P, int32_t F, const floa
 }
 
 namespace avr {
+int validate_render_params(const avr_render_params* p) { return validate(p); }
+
 int launch_irfft(int B, int F, const float* spec, const float* spec2, const float* tw, float* ir,
                  float* ir2, void* stream) {
     AVR_REQUIRE(B >= 1 && F >= 2 && spec && tw && ir, "avr_irfft: bad args");

@@ -127,13 +127,13 @@ class GraphedRender:
             r._staged = None
         return g
 
-    def render_ir(self, rays_o, position_tx, direction_tx=None, *, ray_gain=None):
+    def render_ir(self, rays_o, position_tx, direction_tx=None, *, ray_gain=None, sh_decoder=None):
         """(spectrum [B, F, 2], IR [B, 2(F-1)]) as `AVRRender.render_ir`,
         replayed; the tensors are the instance's static outputs.  Host
         (CPU) pose tensors take the staged path, device ones one copy."""
-        if ray_gain is not None:
-            raise NotImplementedError("GraphedRender does not take ray_gain (directional receivers "
-                                      "render through AVRRender)")
+        if ray_gain is not None or sh_decoder is not None:
+            raise NotImplementedError("GraphedRender does not take ray_gain or sh_decoder (directional "
+                                      "receivers render through AVRRender)")
         if torch.is_grad_enabled() and (rays_o.requires_grad or position_tx.requires_grad or
                                         (direction_tx is not None and direction_tx.requires_grad)):
             raise NotImplementedError("GraphedRender replays a forward-only graph: render poses that require "

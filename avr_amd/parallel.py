@@ -110,10 +110,10 @@ class RayShardedRender(nn.Module):
         self.group = group
         self.shard = shard
 
-    def forward(self, rays_o, position_tx, direction_tx=None, ch_idx=None, *, ray_gain=None):
-        if ray_gain is not None:
-            raise NotImplementedError("RayShardedRender does not take ray_gain (directional receivers "
-                                      "render through AVRRender)")
+    def forward(self, rays_o, position_tx, direction_tx=None, ch_idx=None, *, ray_gain=None, sh_decoder=None):
+        if ray_gain is not None or sh_decoder is not None:
+            raise NotImplementedError("RayShardedRender does not take ray_gain or sh_decoder (directional "
+                                      "receivers render through AVRRender)")
         r = self.renderer
         if self.shard is not None:
             rank, world = self.shard

@@ -12,6 +12,11 @@ Mirrors `renderer.py` of the reference (KMASAHIRO/AVR):
 * keyword-only `ray_gain` on `forward` / `render_ir` (not in the reference):
   a directional receiver as per-ray gains, output [B, C, F, 2]
   (`RenderCoreMC`, `avr_amd.spatial`).
+* keyword-only `sh_decoder` beside `ray_gain` (not in the reference): a
+  complex matrix per frequency bin that decodes the C channels to E ears,
+  output [B, E, F, 2] (`SHDecode`; binaural with `spatial.ambisonic(3)` and
+  `spatial.sh_decoder`); the constructor's `mc_reduce` picks the kernel that
+  sums the rays of a multi-channel receiver.
 * keyword-only `u_azi` on `forward` / `render_ir` (not in the reference): a
   `draw_jitter` result in place of the call's own draw, so the poses of a
   path see one sphere of rays (`avr_amd.auralize.auralize_path`).
@@ -324,11 +329,37 @@ def _gain_stride(gain):
     return gain.size(1) * gain.size(2) if gain.dim() == 3 else 0
 
 
-def _render_core_mc_fwd(attn, signal, gain, p, tables, rays_o, position_tx, dirs):
+def reduce_mc16_max_rays():
+    """Most rays one split of avr_ray_reduce_mc16_fwd may hold."""
+    return int(_lib.load().avr_reduce_mc16_max_rays())
+
+
+MC_REDUCE_MODES = ("auto", "vector", "mfma")
+# "auto" takes the one-pass MFMA reduction from this many channels on
+# (DESIGN.md section 25: the smallest measured C at which it beat the vector
+# kernels at fp32 and fp16 by more than the spread of the runs)
+MC16_MIN_CHANNELS = 5
+
+
+def _use_mc16(mode, p, B, C, signal, n_split):
+    """Whether a C >= 2 channel reduction runs avr_ray_reduce_mc16_fwd."""
+    if mode not in MC_REDUCE_MODES:
+        raise ValueError(f"mc_reduce must be one of {MC_REDUCE_MODES}, got {mode!r}")
+    if mode != "auto":
+        return mode == "mfma"  # the launcher refuses what it cannot run
+    vec = 16 // signal.element_size()
+    return (C >= MC16_MIN_CHANNELS and signal.data_ptr() % 16 == 0 and (p.n_samples * p.T) % vec == 0
+            and -(-p.n_rays // n_split) <= reduce_mc16_max_rays())
+
+
+def _render_core_mc_fwd(attn, signal, gain, p, tables, rays_o, position_tx, dirs, *, mc_reduce="vector"):
     """Stage calls of a C-channel render -> (out [B*C, F, 2], w, delay,
     weights the C = 1 backward multiplies by).  One channel runs the
     single-channel reduction on w*g; more run avr_ray_reduce_mc_fwd, which
-    reads the signal once per block of up to four channels."""
+    reads the signal once per block of up to four channels, or
+    (`mc_reduce`: "mfma", or "auto" where `_use_mc16` says so)
+    avr_ray_reduce_mc16_fwd, which reads it once; both at the same n_split,
+    where they agree bit for bit."""
     dev = signal.device
     B, C = signal.size(0), gain.size(-2)
     S, T = p.n_samples, p.T
@@ -345,7 +376,8 @@ def _render_core_mc_fwd(attn, signal, gain, p, tables, rays_o, position_tx, dirs
         n_split, _ = reduce_mc_splits(p, B, C, sig_code)
         wg = w
         part = torch.empty(n_split, B * C, S, T, dtype=torch.float32, device=dev)
-        _lib.call("avr_ray_reduce_mc_fwd", ctypes_ref(p), B, C, _ptr(signal), sig_code, _ptr(w), _ptr(delay),
+        entry = "avr_ray_reduce_mc16_fwd" if _use_mc16(mc_reduce, p, B, C, signal, n_split) else "avr_ray_reduce_mc_fwd"
+        _lib.call(entry, ctypes_ref(p), B, C, _ptr(signal), sig_code, _ptr(w), _ptr(delay),
                   _ptr(gain), _gain_stride(gain), n_split, _ptr(part), st)
     return _spectrum(p, tables, part, n_split, B * C, dev, st), wg, delay
 
@@ -356,9 +388,11 @@ class RenderCoreMC(torch.autograd.Function):
     signal (gains are constants, like the poses)."""
 
     @staticmethod
-    def forward(ctx, attn, signal, gain, p, tables, rays_o, position_tx, dirs):
-        out, wg, delay = _render_core_mc_fwd(attn, signal, gain, p, tables, rays_o, position_tx, dirs)
-        ctx.p, ctx.tables = p, tables
+    def forward(ctx, attn, signal, gain, p, tables, rays_o, position_tx, dirs, *mc_reduce):
+        """`mc_reduce` (optional, one value): see _render_core_mc_fwd."""
+        out, wg, delay = _render_core_mc_fwd(attn, signal, gain, p, tables, rays_o, position_tx, dirs,
+                                             mc_reduce=mc_reduce[0] if mc_reduce else "vector")
+        ctx.p, ctx.tables, ctx.n_opt = p, tables, len(mc_reduce)
         ctx.save_for_backward(attn, signal, gain, wg, delay)
         return out.view(signal.size(0), gain.size(-2), -1, 2)
 
@@ -384,7 +418,52 @@ class RenderCoreMC(torch.autograd.Function):
                       _ptr(grad_w), st)
         grad_attn = _grad_attn(p, tables, attn, grad_w, st) if ctx.needs_input_grad[0] else None
         return (grad_attn, grad_signal if ctx.needs_input_grad[1] else None,
-                None, None, None, None, None, None)
+                None, None, None, None, None, None) + (None,) * ctx.n_opt
+
+
+class SHDecode(torch.autograd.Function):
+    """out[b,e,f] = sum_k dec[e,k,f] * amb[b,k,f] on [.., F, 2] fp32 tensors
+    (avr_sh_decode_fwd / _bwd); the decoder is a constant."""
+
+    @staticmethod
+    def forward(ctx, amb, dec):
+        B, K, F = amb.shape[:3]
+        out = torch.empty(B, dec.size(0), F, 2, dtype=torch.float32, device=amb.device)
+        _lib.call("avr_sh_decode_fwd", B, dec.size(0), K, F, _ptr(dec), _ptr(amb), _ptr(out), _stream(amb.device))
+        ctx.save_for_backward(dec)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (dec,) = ctx.saved_tensors
+        B, E, F = grad_out.shape[:3]
+        grad_out = grad_out.contiguous()
+        grad_amb = torch.empty(B, dec.size(1), F, 2, dtype=torch.float32, device=grad_out.device)
+        _lib.call("avr_sh_decode_bwd", B, E, dec.size(1), F, _ptr(dec), _ptr(grad_out), _ptr(grad_amb),
+                  _stream(grad_out.device))
+        return grad_amb, None
+
+
+def resolve_sh_decoder(sh_decoder, C, F, dev):
+    """`sh_decoder` [E, K, F] complex or [E, K, F, 2] -> fp32 contiguous
+    [E, K, F, 2] on `dev`; K must be the render's channel count C."""
+    d = torch.as_tensor(sh_decoder).detach()
+    if d.is_complex():
+        d = torch.view_as_real(d.to(torch.complex64))
+    if d.dim() != 4 or d.size(-1) != 2 or d.size(0) < 1:
+        raise ValueError(f"sh_decoder [E, K, F] complex or [E, K, F, 2] expected, got {tuple(d.shape)}")
+    if d.size(1) != C or d.size(2) != F:
+        raise ValueError(f"sh_decoder has K = {d.size(1)} channels and F = {d.size(2)} bins; the render has "
+                         f"{C} and {F}")
+    return _f32_on(d, dev)
+
+
+def sh_decode(amb, dec):
+    """Decode an ambisonic spectrum `amb` [B, K, F, 2] with `dec` ([E, K, F]
+    complex or [E, K, F, 2]) -> [B, E, F, 2]; differentiable in `amb`."""
+    amb = amb.float().contiguous()
+    with _on(amb.device):
+        return SHDecode.apply(amb, resolve_sh_decoder(dec, amb.size(1), amb.size(2), amb.device))
 
 
 def _packed_head_weight(w_master, W, cache, pref, shape_key, st):
@@ -647,6 +726,13 @@ class AVRRender(nn.Module):
         # when that layer hands it over (False: the layer keeps its own
         # threshold_backward; bitwise the same gradients)
         self.head_relu_link = bool(kwargs.get("head_relu_link", True))
+        # the ray reduction of a receiver with two or more channels: "vector"
+        # is the kernels in blocks of 4, 2 and 1 channels, "mfma" the one-pass
+        # MFMA kernel (raises where its launcher refuses), "auto" takes the
+        # latter where _use_mc16 says so; all agree bit for bit
+        self.mc_reduce = kwargs.get("mc_reduce", "auto")
+        if self.mc_reduce not in MC_REDUCE_MODES:
+            raise ValueError(f"mc_reduce must be one of {MC_REDUCE_MODES}, got {self.mc_reduce!r}")
         self._pcache = {}
         self._pcache_lock = threading.Lock()
         # jitter the sampling kernel reads at run time while a HIP graph is
@@ -790,12 +876,16 @@ class AVRRender(nn.Module):
                     self._pcache[key] = p
         return p
 
-    def render_from_network_output(self, attn, signal, geom, ir_out=None, *, ray_gain=None):
+    def render_from_network_output(self, attn, signal, geom, ir_out=None, *, ray_gain=None, sh_decoder=None):
         """Render core (renderer.py:74-124) on given network outputs; the IR
         (utils/criterion.py:71) is also written into `ir_out` when given.
         `ray_gain` ([R], [C,R], [B,C,R] or a callable on geom["dirs"]): a
         directional receiver, out [B, C, F, 2] and ir_out [B, C, 2(F-1)]
-        ([B, F, 2] for a 1-D gain)."""
+        ([B, F, 2] for a 1-D gain).  `sh_decoder` ([E, C, F] complex, with a
+        `ray_gain`): the C-channel spectrum is decoded per bin before the
+        irfft, out [B, E, F, 2] and ir_out [B, E, 2(F-1)]."""
+        if sh_decoder is not None and ray_gain is None:
+            raise ValueError("sh_decoder needs ray_gain (the channels it decodes, e.g. spatial.ambisonic(3))")
         dev, B = geom["device"], geom["B"]
         S = int(self.n_samples)
         native = (torch.float32, torch.float16, torch.bfloat16)
@@ -825,16 +915,20 @@ class AVRRender(nn.Module):
             if ray_gain is not None:
                 gain, flat = resolve_ray_gain(ray_gain, geom)
                 C, F = gain.size(-2), T // 2 + 1
+                dec = None if sh_decoder is None else resolve_sh_decoder(sh_decoder, C, F, dev)
                 args = (attn, signal, gain, p, tables, geom["rays_o"], geom["position_tx"], geom["dirs"])
                 if not (torch.is_grad_enabled() and (attn.requires_grad or signal.requires_grad)):
-                    out = _render_core_mc_fwd(*args)[0].view(B, C, F, 2)
+                    out = _render_core_mc_fwd(*args, mc_reduce=self.mc_reduce)[0].view(B, C, F, 2)
                 else:
-                    out = RenderCoreMC.apply(*args)
+                    out = RenderCoreMC.apply(*args, self.mc_reduce)
+                if dec is not None:
+                    out = SHDecode.apply(out, dec)
                 if ir_out is not None:
-                    _lib.call("avr_irfft", B * C, F, _ptr(out), _ptr(tables.ir_twiddle), _ptr(ir_out), _stream(dev))
+                    _lib.call("avr_irfft", out.size(0) * out.size(1), F, _ptr(out), _ptr(tables.ir_twiddle),
+                              _ptr(ir_out), _stream(dev))
                 if self.propagate_nonfinite:
                     out = _poison_nonfinite(out, (attn, signal), ir_out)
-                return out[:, 0] if flat else out
+                return out[:, 0] if flat and dec is None else out
             if not (torch.is_grad_enabled() and (attn.requires_grad or signal.requires_grad)):
                 # inference: the same native call without the autograd node
                 out = _render_core_fwd(attn, signal, p, tables, geom["rays_o"],
@@ -906,7 +1000,8 @@ class AVRRender(nn.Module):
                 out = _poison_nonfinite(out, (attn, h, weight))
             return out
 
-    def forward(self, rays_o, position_tx, direction_tx=None, ch_idx=None, *, ray_gain=None, u_azi=None):
+    def forward(self, rays_o, position_tx, direction_tx=None, ch_idx=None, *, ray_gain=None, sh_decoder=None,
+                u_azi=None):
         """Render [B, F, 2] (real, imag) spectra; see renderer.py:31-124.
 
         `u_azi` [n_azi] (a `draw_jitter` result, host or device) replaces this
@@ -918,22 +1013,31 @@ class AVRRender(nn.Module):
         [C, R] or [B, C, R], or a callable `dirs [R, 3] -> tensor` called on
         the device with this call's jittered directions.  The output is then
         [B, C, F, 2] ([B, F, 2] for a 1-D gain); None renders the
-        omnidirectional receiver as before."""
-        return self._render(rays_o, position_tx, direction_tx, ch_idx, None, u_azi=u_azi, ray_gain=ray_gain)
+        omnidirectional receiver as before.
 
-    def render_ir(self, rays_o, position_tx, direction_tx=None, ch_idx=None, *, ray_gain=None, u_azi=None):
+        `sh_decoder` ([E, C, F] complex or [E, C, F, 2], e.g.
+        `spatial.sh_decoder(...)` beside `ray_gain=spatial.ambisonic(3)`):
+        the C-channel spectrum is decoded per frequency bin,
+        out[b, e, f] = sum_c D[e, c, f] * out_c[b, f]: [B, E, F, 2], binaural
+        for a two-ear decoder.  C and F must match the render's."""
+        return self._render(rays_o, position_tx, direction_tx, ch_idx, None, u_azi=u_azi, ray_gain=ray_gain,
+                            sh_decoder=sh_decoder)
+
+    def render_ir(self, rays_o, position_tx, direction_tx=None, ch_idx=None, *, ray_gain=None, sh_decoder=None,
+                  u_azi=None):
         """(spectrum [B, F, 2], IR [B, 2(F-1)]): forward plus
         `torch.real(torch.fft.irfft(...))` (utils/criterion.py:71).  Without
         autograd the IR is computed in the same native call; with autograd
         recording it is spectrum_to_ir(out), which differentiates.  With
         `ray_gain` (see forward) both carry the channel axis: [B, C, F, 2]
-        and [B, C, 2(F-1)].  `u_azi`: see forward."""
+        and [B, C, 2(F-1)]; with `sh_decoder` the decoded ears, [B, E, F, 2]
+        and [B, E, 2(F-1)].  `u_azi`: see forward."""
         ir = []
         # the IR inside the render's native call is a forward-only side
         # output; with autograd recording, take it differentiably instead
         grad = torch.is_grad_enabled()
         out = self._render(rays_o, position_tx, direction_tx, ch_idx, None if grad else ir, u_azi=u_azi,
-                           ray_gain=ray_gain)
+                           ray_gain=ray_gain, sh_decoder=sh_decoder)
         if ir:
             return out, ir[0]
         if out.dim() == 4:
@@ -941,12 +1045,16 @@ class AVRRender(nn.Module):
             return out, spectrum_to_ir(out.reshape(B * C, F, 2)).view(B, C, -1)
         return out, spectrum_to_ir(out)
 
-    def _render(self, rays_o, position_tx, direction_tx, ch_idx, ir_slot, u_azi=None, ray_gain=None):
+    def _render(self, rays_o, position_tx, direction_tx, ch_idx, ir_slot, u_azi=None, ray_gain=None,
+                sh_decoder=None):
         """Sampling -> network -> render core; `u_azi` (the azimuth jitter,
         host or device) replaces the CPU draw, as RayShardedRender passes
         rank 0's broadcast draw so every ray shard sees one sphere."""
+        if sh_decoder is not None and ray_gain is None:
+            raise ValueError("sh_decoder needs ray_gain (the channels it decodes, e.g. spatial.ambisonic(3))")
         pts, view, tx, dtx, geom = self.sample(rays_o, position_tx, direction_tx, u_azi=u_azi)
         gain = flat = None
+        ears = None if sh_decoder is None else int(torch.as_tensor(sh_decoder).size(0))
         if ray_gain is not None:
             if self.ray_range is not None:
                 raise NotImplementedError("ray_gain with sharded rays")
@@ -961,7 +1069,8 @@ class AVRRender(nn.Module):
             attn, h, weight, dtype = self.network_fn.forward_fused(*net_in, **kw)
             # one receiver channel folds into the head's compositing weights;
             # more take the network's last layer and the multi-channel core
-            if (gain is None or gain.size(-2) == 1) and self._head_supported(geom, h, weight, dtype):
+            if (gain is None or (gain.size(-2) == 1 and sh_decoder is None)) \
+                    and self._head_supported(geom, h, weight, dtype):
                 # our own networks leave the link of h's ReLU (model.MLP.hidden)
                 link = getattr(self.network_fn, "_relu_link", None) if self.head_relu_link else None
                 self.network_fn.__dict__.pop("_relu_link", None)
@@ -971,27 +1080,32 @@ class AVRRender(nn.Module):
             signal = self.network_fn.finish_signal(h)
             if gain is None:
                 return self.render_from_network_output(attn, signal, geom)
-            return self.render_from_network_output(attn, signal, geom, self._ir_out(signal, geom, gain, flat, ir_slot),
-                                                   ray_gain=gain[0] if flat else gain)
+            return self.render_from_network_output(attn, signal, geom,
+                                                   self._ir_out(signal, geom, gain, flat, ir_slot, ears),
+                                                   ray_gain=gain[0] if flat else gain, sh_decoder=sh_decoder)
         if dtx is not None:
             attn, signal = self.network_fn(pts, view, tx, dtx, **kw)
         else:
             attn, signal = self.network_fn(pts, view, tx, **kw)
-        ir_out = self._ir_out(signal, geom, gain, flat, ir_slot)
+        ir_out = self._ir_out(signal, geom, gain, flat, ir_slot, ears)
         if gain is None:
             return self.render_from_network_output(attn, signal, geom, ir_out)
-        return self.render_from_network_output(attn, signal, geom, ir_out, ray_gain=gain[0] if flat else gain)
+        return self.render_from_network_output(attn, signal, geom, ir_out, ray_gain=gain[0] if flat else gain,
+                                               sh_decoder=sh_decoder)
 
     @staticmethod
-    def _ir_out(signal, geom, gain, flat, ir_slot):
+    def _ir_out(signal, geom, gain, flat, ir_slot, ears=None):
         """The IR buffer of a render_ir call without autograd ([B, n], or
-        [B, C, n] under a gain with a channel axis), appended to `ir_slot`."""
+        [B, C, n] under a gain with a channel axis, [B, E, n] under a decoder
+        with E ears), appended to `ir_slot`."""
         if ir_slot is None:
             return None
         F = signal.size(-1) // 2 + 1
         if F < 2:
             return None
         lead = (geom["B"],) if gain is None or flat else (geom["B"], gain.size(-2))
+        if ears is not None:
+            lead = (geom["B"], ears)
         ir_out = torch.empty(*lead, 2 * (F - 1), dtype=torch.float32, device=geom["device"])
         ir_slot.append(ir_out)
         return ir_out

@@ -187,6 +187,31 @@ int avr_ray_reduce_mc_fwd(const avr_render_params* p, int32_t B, int32_t C, cons
 int avr_reduce_mc_splits(const avr_render_params* p, int32_t B, int32_t C, int32_t sig_dtype,
                          int32_t* n_split, int32_t* max_rays);
 
+/* avr_ray_reduce_mc_fwd's contract (same arguments, same `part`) with all C
+ * channels, 1 <= C <= 16, in one pass over the signal: the reduction as a
+ * [16 x rays] x [rays x t] product on v_mfma_f32_16x16x4_f32, rays ascending,
+ * so for finite inputs every element equals avr_ray_reduce_mc_fwd's at the
+ * same n_split (pass avr_reduce_mc_splits' value).  Only the 16-byte vector
+ * form exists: a signal that is not 16-byte aligned, or S*T not a multiple of
+ * the 16-byte vector's elements, is AVR_E_CONFIG before any launch.  A split
+ * holds at most avr_reduce_mc16_max_rays() rays (68 bytes of LDS each); more
+ * are AVR_E_ARG before any launch. */
+int avr_ray_reduce_mc16_fwd(const avr_render_params* p, int32_t B, int32_t C, const void* signal,
+                            int32_t sig_dtype, const float* w, const int32_t* delay,
+                            const float* gain, int64_t gain_b_stride, int32_t n_split, float* part,
+                            void* stream);
+int32_t avr_reduce_mc16_max_rays(void);
+
+/* ---- binaural decode of an ambisonic spectrum ---------------------------
+ * out[B][E][F][2] = sum_k dec[E][K][F][2] * amb[B][K][F][2] (complex, k
+ * ascending, four fmaf per term), any E >= 1, 1 <= K <= 16; and its adjoint
+ * for amb, grad_amb[b,k,f] = sum_e conj(dec[e,k,f]) * grad_out[b,e,f] (the
+ * decoder is a constant). */
+int avr_sh_decode_fwd(int32_t B, int32_t E, int32_t K, int32_t F, const float* dec, const float* amb,
+                      float* out, void* stream);
+int avr_sh_decode_bwd(int32_t B, int32_t E, int32_t K, int32_t F, const float* dec,
+                      const float* grad_out, float* grad_amb, void* stream);
+
 /* ---- a9/a10/a11/a12 (frequency half): DFT + phase + sum over samples ---
  * z[b,s,t] = pl[shift[s]+t] * [t < T-1-shift[s]] * sum_k part[k,b,s,t]
  * spart[B][P][F][2], P = ceil(S/32) * k_split: partial spectra
